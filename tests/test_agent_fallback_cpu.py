@@ -360,7 +360,7 @@ def test_bench_fault_spec_targets_one_rank():
     assert bench.fault_for_rank("", 3) == ""
     with pytest.raises(SystemExit):
         bench.fault_for_rank("skip_comm_init", 0)
-    a = bench.parse_args(["--gpus", "2"])
+    a = bench.parse_args(["--full", "--gpus", "2"])  # the traced collectives are part of a --full run
     assert a.comm_trace == "auto" and a.comm_init_timeout_s == 60.0
 
 
