@@ -150,6 +150,100 @@ def reference_pack(raw: np.ndarray, ts_ns: np.ndarray, counter_of: np.ndarray,
     return deltas, derived, flags
 
 
+HISTORY_MAX_BUCKETS = 4096
+HISTORY_MAX_WINDOW_NS = 1 << 51
+
+HISTORY_HEADER_DTYPE = np.dtype([
+    ("seq_begin", "<u8"), ("seq_end", "<u8"), ("oldest_ts_ns", "<u8"), ("newest_ts_ns", "<u8"),
+    ("stale", "<u8"), ("truncated", "<u4"), ("buckets", "<u4"), ("t0_ns", "<u8"), ("t1_ns", "<u8"),
+])
+assert HISTORY_HEADER_DTYPE.itemsize == 64
+
+HISTORY_BUCKET_DTYPE = np.dtype([
+    ("first_seq", "<u8"), ("n_slots", "<u4"), ("n_reset", "<u4"), ("dt_us_sum", "<f8"), ("reserved", "<u8"),
+    ("n", "<u4", (MAX_DERIVED,)), ("min", "<f4", (MAX_DERIVED,)), ("max", "<f4", (MAX_DERIVED,)),
+    ("wsum", "<f8", (MAX_DERIVED,)), ("w", "<f8", (MAX_DERIVED,)),
+])
+assert HISTORY_BUCKET_DTYPE.itemsize == 480
+
+
+def derived_mask(pass_id) -> np.ndarray:
+    """dynoDerivedMask (SlotFormat.h), elementwise."""
+    p = np.asarray(pass_id)
+    return np.where(p == PASS_PRECISION, MASK_PRECISION, np.where(p == PASS_MFMA, MASK_MFMA, MASK_MAIN))
+
+
+def history_args_valid(ring_slots: int, seq_lo: int, seq_hi: int, t0: int, t1: int, buckets: int) -> bool:
+    """Mirror of dynoHistoryArgsValid (HistoryReduce.h)."""
+    return (ring_slots > 0 and ring_slots & (ring_slots - 1) == 0 and 0 <= seq_lo <= seq_hi
+            and seq_hi - seq_lo <= ring_slots and t0 < t1 and t1 - t0 < HISTORY_MAX_WINDOW_NS
+            and 1 <= buckets <= HISTORY_MAX_BUCKETS)
+
+
+def history_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int,
+                      buckets: int, phase: int | None = None):
+    """The yardstick of the history query (kernels/history.hip and its host twin
+    HistoryReduce.h): (header, buckets) as HISTORY_HEADER_DTYPE / HISTORY_BUCKET_DTYPE.
+
+    slots: the ring image (SLOT_DTYPE[ring_slots]; seq s lives at s & (ring_slots - 1));
+    [seq_lo, seq_hi) the valid range; [t0, t1) the window; phase: None = no filter.
+    Defined for a ring in time order (an overwritten position, seq field > its
+    sequence number, counts as older than anything).  Sums are float64 in seq order."""
+    if not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, buckets):
+        raise ValueError("history query arguments out of range")
+    assert slots.dtype == SLOT_DTYPE and len(slots) == ring_slots
+    hdr = np.zeros((), dtype=HISTORY_HEADER_DTYPE)
+    out = np.zeros(buckets, dtype=HISTORY_BUCKET_DTYPE)
+    hdr["buckets"], hdr["t0_ns"], hdr["t1_ns"] = buckets, t0, t1
+    seqs = np.arange(seq_lo, seq_hi, dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    if len(seqs):
+        oldest_valid = int(x["seq"][0]) == seq_lo
+        hdr["oldest_ts_ns"] = int(x["host_ts_ns"][0]) if oldest_valid else 0
+        hdr["newest_ts_ns"] = int(x["host_ts_ns"][-1]) if int(x["seq"][-1]) == seq_hi - 1 else 0
+        hdr["truncated"] = int(not oldest_valid or t0 < int(x["host_ts_ns"][0]))
+    key = np.where(x["seq"] > seqs, np.uint64(0), x["host_ts_ns"])
+    begin = seq_lo + int(np.count_nonzero(key < np.uint64(t0)))
+    end = seq_lo + int(np.count_nonzero(key < np.uint64(t1)))
+    hdr["seq_begin"], hdr["seq_end"] = begin, end
+    sel = slice(begin - seq_lo, end - seq_lo)
+    x, seqs = x[sel], seqs[sel]
+    ts = x["host_ts_ns"]
+    ok = (x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1))
+    hdr["stale"] = int(np.count_nonzero(~ok))
+    x, seqs, ts = x[ok], seqs[ok], x["host_ts_ns"][ok]
+    # exact unsigned 64-bit bucket index: (ts - t0) * B < 2^63 by the window limit
+    b = (((ts - np.uint64(t0)) * np.uint64(buckets)) // np.uint64(t1 - t0)).astype(np.int64)
+    np.add.at(out["n_slots"], b, 1)
+    np.add.at(out["n_reset"], b, ((x["flags"] & SLOT_RESET) != 0).astype(np.uint32))
+    first = np.full(buckets, np.iinfo(np.uint64).max, dtype=np.uint64)
+    np.minimum.at(first, b, seqs)
+    out["first_seq"] = np.where(out["n_slots"] > 0, first, 0)
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    use = ((x["flags"] & SLOT_FIRST) == 0) & (dtf > 0) & np.isfinite(dtf)
+    if phase is not None:
+        use &= x["phase"] == np.uint32(phase)
+    x, b, dt = x[use], b[use], dtf[use].astype(np.float64)
+    np.add.at(out["dt_us_sum"], b, dt)
+    mask = derived_mask(x["pass"])
+    for d in range(len(DERIVED)):
+        v = x["derived"][:, d]
+        take = ((mask >> d) & 1).astype(bool) & np.isfinite(v)
+        bd, vd, wd = b[take], v[take], dt[take]
+        n = np.zeros(buckets, dtype=np.uint32)
+        np.add.at(n, bd, 1)
+        mn = np.full(buckets, np.inf, dtype=np.float32)
+        mx = np.full(buckets, -np.inf, dtype=np.float32)
+        np.minimum.at(mn, bd, vd)
+        np.maximum.at(mx, bd, vd)
+        out["n"][:, d] = n
+        out["min"][:, d] = np.where(n > 0, mn, 0)
+        out["max"][:, d] = np.where(n > 0, mx, 0)
+        np.add.at(out["wsum"][:, d], bd, vd.astype(np.float64) * wd)
+        np.add.at(out["w"][:, d], bd, wd)
+    return hdr, out
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

@@ -1070,6 +1070,13 @@ void Agent::controlLoop() {
         (void)ctl_->syncSend(ipc::Message::fromString(ipc::kMsgKernelTraceResult, res.dump()), msg->src, 3, 10000);
         continue;
       }
+      if (req.contains("op") && req.at("op").isString() && req.at("op").asString() == "history") {
+        // this rank's slot history of a window, reduced on its GPU (every
+        // rank answers: each GPU's ring holds its own history)
+        (void)ctl_->syncSend(ipc::Message::fromString(ipc::kMsgKernelTraceResult, historyRequest(req, res).dump()),
+                             msg->src, 3, 10000);
+        continue;
+      }
       if (req.contains("op") && req.at("op").isString() && req.at("op").asString() == "comm_trace") {
         (void)ctl_->syncSend(ipc::Message::fromString(ipc::kMsgKernelTraceResult, commTraceRequest(req, res).dump()),
                              msg->src, 3, 10000);
@@ -1524,6 +1531,18 @@ void Agent::releaseDevice() {
       m.used = false;
     }
   }
+  {
+    std::lock_guard<std::mutex> g(histMu_);  // (device sync at stop: no query is in flight)
+    freeDev(dHistWs_);
+    freeDev(dHistOut_);
+    freeHost(hHistOut_);
+    destroyEvent(histT0_);
+    destroyEvent(histT1_);
+    destroyEvent(histDone_);
+    histPending_ = false;
+    if (histStream_) hipWarn(hipStreamDestroy(histStream_), "hipStreamDestroy history");
+    histStream_ = nullptr;
+  }
   freeHost(hPhase_);
   freeDev(dAgree_);
   freeHost(hAgree_);
@@ -1737,6 +1756,10 @@ Json Agent::stats() const {
     if (samplerClockValid_) j["sampler_cpu_pct"] = 100.0 * threadCpuSec(samplerClock_) / el;
     if (consumerClockValid_) j["consumer_cpu_pct"] = 100.0 * threadCpuSec(consumerClock_) / el;
   }
+  // history queries answered, and the last one's kernel time from its events
+  // (a pack_mode host ring: the host twin's time)
+  j["history_queries"] = static_cast<unsigned long long>(historyQueries_.load());
+  j["history_last_us"] = historyLastUs_.load();
   j["last_error"] = lastError_;
   if (sampler_) j["agent"] = sampler_->agent().name;
   if (cfg_.isRoot()) {

@@ -265,6 +265,48 @@ Json GpuAgentRegistry::commTrace(const std::vector<int>& pids, int durationMs, i
       durationMs + slackMs, send);
 }
 
+Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, const std::string& pathPrefix,
+                               const Sender& send, int timeoutMs) {
+  auto targets = agents(pids);
+  if (targets.empty()) {
+    Json out = Json::object();
+    out["status"] = "failed: no GPU agents registered" + std::string(pids.empty() ? "" : " for these pids");
+    return out;
+  }
+  std::map<int, std::string> paths;  // key(pid, rank) -> the file this daemon named
+  Json out = ask(
+      targets,
+      [&](const GpuAgentEntry& a) {
+        Json req = query.isObject() ? query : Json::object();
+        req["op"] = "history";
+        const std::string path = pathPrefix + std::to_string(a.pid) + "_r" + std::to_string(a.rank) + ".json";
+        req["out_path"] = path;
+        paths[key(a.pid, a.rank)] = path;
+        return req;
+      },
+      timeoutMs, send);
+  // an answer too large for a datagram left its buckets in the named file
+  for (auto& r : out["results"].asArray()) {
+    if (!r.isObject() || !r.contains("buckets_path")) continue;
+    r.asObject().erase("buckets_path");
+    const int pid = static_cast<int>(getI(r, "pid"));
+    auto it = paths.find(key(pid, static_cast<int>(getI(r, "rank"))));
+    if (it == paths.end()) continue;  // not a target of this request
+    const std::string p = it->second;
+    paths.erase(it);  // one reply per target
+    std::string body, why;
+    Json arr;
+    if (!readAgentFile(p, pid, &body, &why)) {
+      r["status"] = "failed: " + why;
+    } else if (!Json::tryParse(body, &arr) || !arr.isArray()) {
+      r["status"] = "failed: unreadable buckets file";
+    } else {
+      r["buckets"] = std::move(arr);
+    }
+  }
+  return out;
+}
+
 std::vector<Json> GpuAgentRegistry::counterTracks(uint64_t t0Ns, uint64_t t1Ns, int device,
                                                  const std::string& pathPrefix, const Sender& send,
                                                  int timeoutMs) {

@@ -67,6 +67,13 @@ class GpuAgentRegistry {
   // Ask every matching agent for its RCCL collectives over durationMs
   // (CommTracer) and collect the replies.
   Json commTrace(const std::vector<int>& pids, int durationMs, int last, const Sender& send, int slackMs = 5000);
+  // Ask every matching agent (every rank: each GPU's ring holds its own
+  // history) for its slot history of a window, reduced on its GPU (IPC "gktr"
+  // op "history"; `query` carries t0_ns / t1_ns or last_s, buckets, phase,
+  // metrics).  An answer too large for a datagram comes through the file
+  // "<pathPrefix><pid>_r<rank>.json", which is read and removed.
+  Json history(const std::vector<int>& pids, const Json& query, const std::string& pathPrefix, const Sender& send,
+               int timeoutMs = 8000);
   // Ask every live agent for its 1 kHz counter tracks of [t0Ns, t1Ns]
   // (CLOCK_MONOTONIC) of GPU `device` (-1: all); aggregators write them to
   // "<pathPrefix><pid>.json".  Returns the events of every agent that had
