@@ -108,7 +108,7 @@ struct AgentConfig {
                                      // as a non-root gather member (no receive buffers, no
                                      // consumer; the 1-rank gather runs in place)
   uint64_t ringSlots = 1ull << 20;   // slot history per GPU: 2^20 = 256 MiB, ~17 min at 1 kHz,
-                                     // in HBM (pack_mode step / device; up to 2^30 slots =
+                                     // in HBM (pack_mode step; up to 2^30 slots =
                                      // 256 GiB of the 288 GB).  pack_mode host keeps it in
                                      // pinned host memory, capped at 2^24 slots (4 GiB): a
                                      // larger request is clamped, logged and reported
@@ -156,8 +156,9 @@ class Agent {
   bool step(hipStream_t stream, std::string* err, bool catchUp = false);
   // Block until every enqueued drain has been consumed (rank 0).
   void flush();
-  // Ask the sampler thread to pack its partially filled batch now; returns
-  // once it has been launched (so a following step() gathers it).
+  // pack_mode host: ask the sampler thread to pack its partially filled batch
+  // now; returns once it is in the host ring (so a following step() gathers
+  // it).  Step packing stages every sample as it is taken: nothing to do.
   void packPending();
   void pause();
   void resume();
@@ -218,7 +219,6 @@ class Agent {
   Json sqttRequest(const Json& req, Json res);
   Json dispatchCountersRequest(const Json& req, Json res);
   Json commTraceRequest(const Json& req, Json res);
-  bool flushBatch(int nstaged, std::string* err);
   void consumerLoop();
   void logInterval();  // consumer: one interval's records -> the log queue
   void logLoop();      // log thread: the queued records -> the sinks
@@ -238,6 +238,23 @@ class Agent {
   // waiting behind the trainer's queued work on the null stream
   bool setupLayout(PassState& ps, const std::vector<uint64_t>& ids, std::string* err, hipStream_t copy = nullptr);
   void switchPass();  // sampler thread: stop the current pass, start the next
+  // start()'s stages, in the order it runs them (Agent.cpp)
+  bool configure(const AgentConfig& cfg, std::string* err);
+  void dropFailedStart();
+  bool joinCommunicator(const void* uid, size_t idLen, std::string* err);
+  bool resolveRocprofAgent(std::string* err);
+  void resetRunState();
+  void resolveAutoSampler(const std::vector<CounterPassSpec>& specs);
+  bool attachSidecar(const std::vector<CounterPassSpec>& specs, std::string* err);
+  bool buildOwnPasses(const std::vector<CounterPassSpec>& specs, std::string* err);
+  bool allocRing(std::string* err);
+  bool allocStaging(std::string* err);
+  bool allocGatherBuffers(std::string* err);
+  bool openShmMailbox(const void* uid, size_t idLen, std::string* err);
+  void setupAggregator(const std::vector<CounterPassSpec>& specs);
+  bool discoverLayouts(std::string* err);
+  void launchThreads();
+  std::string pinThreads();  // sampler / consumer onto the GPU's local CPUs; what it did
   void releaseDevice();
   void waitSamplesThrough(uint64_t t1) const;  // rank 0: samples up to t1 ingested (<= 1 s)
 
@@ -416,9 +433,10 @@ class Agent {
   DynoSlot* hRing_ = nullptr;
   std::vector<double> hCarry_;
   std::atomic<uint64_t> hostHead_{0};
-  void hostPackBatch(int nstaged, const uint8_t* stage);
+  void hostPackBatch(int nstaged);  // sampler thread: hStage_'s first nstaged samples -> the host ring
   // world 1 / shm: header + ring slots [first, first + count) into a host buffer
   void hostGatherBlock(uint8_t* dst, const GatherRange& rg, uint64_t head, uint32_t cap) const;
+  void hostGatherLocal(uint64_t head);  // world 1 / shm: this step's gather, on the calling thread
   uint8_t* dSend_ = nullptr;
   size_t sendBytes_ = 0;
   static constexpr int kRecv = 4;
@@ -440,9 +458,10 @@ class Agent {
   uint64_t seq_ = 0;
   uint64_t prevTs_ = 0;
   std::mutex packMu_;
-  // One event per pack launch with the ring head it completes.  step()
-  // gathers through the newest mark whose event has COMPLETED (host query),
-  // so the trainer's stream never waits on the low-priority pack stream.
+  // pack_mode step: one event per step pack launch (recorded behind it on the
+  // trainer's stream) with the staging head it packs through.  The sampler
+  // reuses staging entries below the newest mark whose event has completed
+  // (stepCompleted, a host query); history(wait) waits on the newest mark.
   struct PackMark {
     hipEvent_t ev = nullptr;
     uint64_t head = 0;
@@ -451,7 +470,6 @@ class Agent {
   static constexpr int kPackMarks = 16;
   PackMark packMarks_[kPackMarks];
   int packMarkNext_ = 0;
-  uint64_t completedPackHead();  // newest completed mark's head (packMu_)
   uint64_t gatheredHost_ = 0;   // slots already handed to a gather (stepMu_)
 
   // Collective payload sizing (GatherPlan.h): each gather max-reduces the
@@ -472,7 +490,10 @@ class Agent {
   std::atomic<uint64_t> captureSkips_{0};  // step() calls inside a hipGraph capture
   std::atomic<uint64_t> catchUpGathers_{0};  // step(catchUp) gathers sent at the full payload
   bool gatherCollective(hipStream_t stream, uint64_t head, std::string* err, bool catchUp);
-  bool gatherLocal(hipStream_t stream, uint64_t head, std::string* err);
+  // the gather paths' shared bookkeeping (stepMu_): a range has been sent;
+  // receive buffer `slot` is the consumer's (host: filled on the host, no event)
+  void commitGather(const GatherRange& rg);
+  void handToConsumer(int slot, uint32_t cap, bool host);
 
   // Gather latency on the trainer's stream (gather_prep through the end of the
   // collective / drain hand-off): timing events around each gather, harvested

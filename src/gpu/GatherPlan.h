@@ -46,8 +46,9 @@ struct GatherRange {
 // Slots [first, first + count) of a ring whose pack cursor is `head`, when
 // slots before `gathered` were already sent and the payload holds `cap`.
 // Pending slots further than half the ring behind the head are dropped:
-// the pack stream writes the head concurrently with the gather reading the
-// tail, and the half-ring margin keeps the two apart.
+// the packer (the next step's pack launch, or the sampler thread with host
+// packing) writes at the head while a gather still reads the tail, and the
+// half-ring margin keeps the two apart.
 inline GatherRange planGatherRange(uint64_t head, uint64_t gathered, uint32_t cap, uint64_t ringCapacity) {
   GatherRange r;
   const uint64_t window = std::max<uint64_t>(ringCapacity / 2, 1);
@@ -81,9 +82,9 @@ class GatherSizer {
   // Payload (slots per rank) of a gather whose agreed lagged need is maxNeed:
   // the need plus an eighth and one quantum of headroom, rounded up to the
   // quantum, within [minCap, maxCap].  Step-to-step jitter of one rank's
-  // pending count is about one pack batch (32 slots: step() only sees
-  // completed packs) plus the step-time variation; what does not fit waits
-  // one step in the backlog.
+  // pending count is about one pack batch (32 slots: host packing publishes
+  // its head a batch at a time) plus the step-time variation; what does not
+  // fit waits one step in the backlog.
   uint32_t capForNeed(uint64_t maxNeed) const {
     uint64_t c = maxNeed + maxNeed / 8 + kQuantum;
     c = (c + kQuantum - 1) / kQuantum * kQuantum;

@@ -1,5 +1,5 @@
-// Derived metrics of one packed counter sample, shared by the CDNA4 pack
-// kernel (src/gpu/kernels/sampler_pack.hip, thread 0 of each workgroup) and
+// Derived metrics of one packed counter sample, shared by the CDNA4 step pack
+// kernel (src/gpu/kernels/step_pack.hip, lane 0 of each workgroup) and
 // its host twin hostPack() (DeviceMonitor.cpp, the daemon's out-of-process
 // path), so the in-process and daemon records agree bit for bit.
 //

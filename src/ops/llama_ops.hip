@@ -609,13 +609,12 @@ __global__ __launch_bounds__(kBlock) void xent_bwd_t_kernel(
 // (moments in bf16, fp32 math, decoupled weight decay, bias correction).
 // The tensor list travels BY VALUE in the kernel arguments, up to
 // kAdamPerLaunch tensors per launch (~3.3 KB of kernarg), so a step needs no
-// device-side pointer table and no host->device copy at all (a per-step
-// pinned-table upload measurably disturbed the counter sampler's own
-// copies).  Each tensor is cut into kAdamChunk-element chunks; the grid is
-// one workgroup per chunk (never persistent: workgroups retire every few
-// microseconds, so the sampler's low-priority pack kernels get CUs while the
-// update runs) and a workgroup finds its tensor by a binary search over the
-// chunk prefix sums.  Aligned tensors (n % 8 == 0 and all four pointers
+// device-side pointer table and no host->device copy at all.  Each tensor is
+// cut into kAdamChunk-element chunks; the grid is one workgroup per chunk
+// (never persistent: workgroups retire every few microseconds, so another
+// stream's kernels get CUs while the update runs) and a workgroup finds its
+// tensor by a binary search over the chunk prefix sums.
+// Aligned tensors (n % 8 == 0 and all four pointers
 // 16-byte aligned) take the 16-byte vector path, others the scalar path.
 // 14 bytes of HBM traffic per parameter: the update is purely HBM-bound.
 struct AdamTensor {
