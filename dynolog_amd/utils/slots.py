@@ -244,6 +244,68 @@ def history_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: i
     return hdr, out
 
 
+HISTORY_MAX_QUANTILES = 4
+HISTORY_QUANTILE_MAX_BUCKETS = 512
+HISTORY_QUANTILES_DTYPE = np.dtype([("q", "<f4", (MAX_DERIVED, HISTORY_MAX_QUANTILES))])
+assert HISTORY_QUANTILES_DTYPE.itemsize == 256
+
+
+def history_key(values: np.ndarray) -> np.ndarray:
+    """dynoHistoryKey (HistoryReduce.h): the uint32 whose unsigned order is the
+    order of the float32 values, -0.0 before +0.0."""
+    bits = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32)
+    return np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def history_key_bits(keys: np.ndarray) -> np.ndarray:
+    """Inverse of history_key: the float32 bit patterns."""
+    keys = np.asarray(keys, dtype=np.uint32)
+    return np.where(keys & np.uint32(0x80000000), keys & np.uint32(0x7FFFFFFF), ~keys).astype(np.uint32)
+
+
+def history_rank(q_ppm: int, n: int) -> int:
+    """dynoHistoryRank: the nearest rank of q_ppm among n samples, in [1, n]; 0 for n == 0."""
+    return 0 if n == 0 else min(max((q_ppm * n + 999999) // 1000000, 1), n)
+
+
+def history_quantiles_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int,
+                                buckets: int, q_ppm, phase: int | None = None) -> np.ndarray:
+    """The yardstick of a history query's quantiles (SlotFormat.h
+    DynoHistoryQuantiles): HISTORY_QUANTILES_DTYPE[buckets].  Arguments as for
+    history_reference, whose n[d] counts exactly the population of each
+    quantile; q_ppm: up to 4 integers in [0, 1000000].  By sample count, nearest
+    rank, over the sorted uint32 keys: the answer is a sample's own bits."""
+    q_ppm = [int(q) for q in q_ppm]
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, buckets) or len(q_ppm) > HISTORY_MAX_QUANTILES
+            or any(q < 0 or q > 1000000 for q in q_ppm) or (q_ppm and buckets > HISTORY_QUANTILE_MAX_BUCKETS)):
+        raise ValueError("history quantile query arguments out of range")
+    assert slots.dtype == SLOT_DTYPE and len(slots) == ring_slots
+    out = np.zeros(buckets, dtype=HISTORY_QUANTILES_DTYPE)
+    seqs = np.arange(seq_lo, seq_hi, dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    key = np.where(x["seq"] > seqs, np.uint64(0), x["host_ts_ns"])
+    sel = slice(int(np.count_nonzero(key < np.uint64(t0))), int(np.count_nonzero(key < np.uint64(t1))))
+    x, seqs = x[sel], seqs[sel]
+    ts = x["host_ts_ns"]
+    x = x[(x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1))]
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    use = ((x["flags"] & SLOT_FIRST) == 0) & (dtf > 0) & np.isfinite(dtf)
+    if phase is not None:
+        use &= x["phase"] == np.uint32(phase)
+    x = x[use]
+    b = (((x["host_ts_ns"] - np.uint64(t0)) * np.uint64(buckets)) // np.uint64(t1 - t0)).astype(np.int64)
+    mask = derived_mask(x["pass"])
+    for d in range(len(DERIVED)):
+        v = x["derived"][:, d]
+        take = ((mask >> d) & 1).astype(bool) & np.isfinite(v)
+        keys, bd = history_key(v[take]), b[take]
+        for bucket in np.unique(bd):
+            k = np.sort(keys[bd == bucket])
+            picked = np.array([k[history_rank(q, len(k)) - 1] for q in q_ppm], dtype=np.uint32)
+            out["q"][bucket, d, :len(q_ppm)] = history_key_bits(picked).view(np.float32)
+    return out
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

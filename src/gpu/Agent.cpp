@@ -1608,6 +1608,9 @@ void Agent::releaseDevice() {
     freeDev(dHistWs_);
     freeDev(dHistOut_);
     freeHost(hHistOut_);
+    freeDev(dHistQWs_);
+    freeDev(dHistQ_);
+    freeHost(hHistQ_);
     destroyEvent(histT0_);
     destroyEvent(histT1_);
     destroyEvent(histDone_);
@@ -1832,6 +1835,7 @@ Json Agent::stats() const {
   // (a pack_mode host ring: the host twin's time)
   j["history_queries"] = static_cast<unsigned long long>(historyQueries_.load());
   j["history_last_us"] = historyLastUs_.load();
+  j["history_quantile_queries"] = static_cast<unsigned long long>(historyQuantileQueries_.load());
   j["last_error"] = lastError_;
   if (sampler_) j["agent"] = sampler_->agent().name;
   if (cfg_.isRoot()) {
