@@ -42,6 +42,8 @@
 #include "gpu/SlotAggregator.h"
 #include "gpu/SlotBroadcast.h"
 #include "gpu/SlotFormat.h"
+#include "gpu/StageRings.h"
+#include "gpu/StepPassTable.h"
 #include "ring/RingBuffer.h"
 #include "sinks/Logger.h"
 
@@ -231,16 +233,18 @@ class Agent {
     std::unique_ptr<CounterSampler> sampler;
     DynoAgentConsts consts{};
     size_t R = 0;  // raw instance values per sample
-    int* dPerm = nullptr;
-    int* dSegStart = nullptr;
-    int* dSegLen = nullptr;
     std::vector<int> counterOf;  // record index -> counter slot (host pack)
     uint32_t counterMask = 0;    // delta[] positions this set selects (every slot carries it)
   };
-  // copy: nullptr = synchronous copies on the null stream (at start); a
-  // non-blocking stream keeps a mid-run setup (the sidecar fallback) from
-  // waiting behind the trainer's queued work on the null stream
-  bool setupLayout(PassState& ps, const std::vector<uint64_t>& ids, std::string* err, hipStream_t copy = nullptr);
+  // a pass's sampler, configured (nothing programmed), its constants and raw count
+  bool makePass(const CounterPassSpec& sp, PassState* ps, std::string* err) const;
+  // The first sample of a pass discovers its record layout: select, start,
+  // sample, lay out (pack_mode step: pass-table entry idx), stop unless
+  // keepRunning.  A pass that fails is left stopped.  copy: StepPassTable::set.
+  bool firstSample(PassState& ps, uint32_t idx, bool keepRunning, hipStream_t copy, std::string* err);
+  bool setupLayout(PassState& ps, const std::vector<uint64_t>& ids, uint32_t idx, hipStream_t copy, std::string* err);
+  // the daemon's counter layouts as pass-table entries [base, base + layouts)
+  bool setDaemonLayouts(const SlotBroadcastReader& r, uint32_t base, hipStream_t copy, std::string* err);
   void switchPass();  // sampler thread: stop the current pass, start the next
   // start()'s stages, in the order it runs them (Agent.cpp)
   bool configure(const AgentConfig& cfg, std::string* err);
@@ -262,67 +266,31 @@ class Agent {
   void releaseDevice();
   void waitSamplesThrough(uint64_t t1) const;  // rank 0: samples up to t1 ingested (<= 1 s)
 
-  // pack_mode step (stepPack_).  A staging ring holds entry e at [e & (slots
-  // - 1)]: its DynoStepMeta in meta, its raw values at raw + (e & (slots - 1))
-  // * stepStride_.  The sampler thread publishes entries [0, stepHead_); step()
-  // packs [stepTail_, stepHead_); entries below stepDone_ (the newest
-  // completed launch's end) are free to overwrite, except entry stepDone_ - 1,
-  // the predecessor of the next launch's first sample.
-  // Growth: once half the current ring holds unpacked entries, a helper
-  // thread allocates one twice as large; the sampler then publishes entry
-  // `first` on into it, with entry first - 1 copied in as its predecessor.
-  // step() packs a range spanning rings with one launch per ring.  Older
-  // rings stay allocated until stop() (a launch may still read them).
-  struct StageRing {
-    uint8_t* mem = nullptr;
-    DynoStepMeta* meta = nullptr;
-    double* raw = nullptr;
-    uint64_t slots = 0;
-    uint64_t first = 0;  // first entry published into this ring
-    DynoStepMeta* metaOf(uint64_t e) const { return meta + (e & (slots - 1)); }
-    double* rawOf(uint64_t e, int stride) const { return raw + (e & (slots - 1)) * static_cast<uint64_t>(stride); }
-  };
+  // pack_mode step (stepPack_): the sampler thread stages into stage_
+  // (StageRings.h), step() packs [stepTail_, stage_.head())
   bool stepPack_ = false;
   int stepStride_ = 0;
-  std::mutex stageMu_;                                  // stageRings_ (sampler switch vs step())
-  std::vector<std::unique_ptr<StageRing>> stageRings_;  // back() = the current ring
-  StageRing* stageCur_ = nullptr;                       // sampler thread's current ring
-  std::atomic<uint64_t> stepSlots_{0};                  // the current ring's size (stats)
-  uint64_t stageMaxSlots_ = 0;
-  std::thread stageGrowThread_;
-  std::atomic<StageRing*> stageGrown_{nullptr};         // allocated, not yet switched to
-  bool stageGrowPending_ = false;                       // sampler thread
-  std::atomic<uint64_t> stageGrows_{0}, stageGrowFails_{0};
-  bool allocStageRing(StageRing* r, uint64_t slots, std::string* err);
-  // sampler / sidecar thread, before publishing entry sh: room for it (a
-  // full ring counts stageFull_), growth requested / switched to
-  StageRing* stageFor(uint64_t sh);
-  std::atomic<uint64_t> stepHead_{0}, stepDone_{0};
+  StageRings stage_;
   uint64_t stepTail_ = 0;            // stepMu_
   uint64_t stepLastTs_ = 0;          // sampler thread: the last staged sample
   std::vector<double> stepScratch_;  // sampler thread: the read, before its streaming copy
   bool stepHaveLast_ = false;
-  DynoStepPass* dStepPasses_ = nullptr;
+  StepPassTable stepPasses_;
   bool setupStepPasses(std::string* err);
   // one launch: pack [stepTail_, head) and, with out, build the payload
   bool launchStepPack(hipStream_t stream, uint64_t head, uint8_t* out, const DynoGatherHeader* gh,
                       uint64_t* needOut, uint64_t need, std::string* err);
   bool stepGatherLocal(hipStream_t stream, uint64_t head, std::string* err);
-  uint64_t stepCompleted();          // newest completed launch's end (packMu_)
-  std::atomic<uint64_t> stepLaunches_{0}, stagePacked_{0}, stageFull_{0};
+  uint64_t newestCompletedPack();    // its end, by a host query of the pack marks (packMu_)
+  std::atomic<uint64_t> stepLaunches_{0}, stagePacked_{0};
   // sampler "daemon" (the sidecar)
   std::atomic<bool> sidecar_{false};  // the sidecar machinery is on (from start, or a late join)
   std::unique_ptr<SlotBroadcastReader> sidecarReader_;
   std::string sidecarName_;
   std::atomic<uint64_t> sidecarPciLoc_{0};  // pci_loc in the broadcast's header
   // raw sidecar: the daemon's counter layouts as step-kernel passes
-  bool sidecarRaw_ = false;
-  struct SidecarLayout {
-    int* dPerm = nullptr;
-    int* dSegStart = nullptr;
-    int* dSegLen = nullptr;
-  };
-  std::vector<SidecarLayout> sidecarLayouts_;
+  std::atomic<bool> sidecarRaw_{false};
+  std::atomic<uint32_t> sidecarLayouts_{0};  // the daemon's layouts in the pass table
   uint64_t sidecarLastSrc_ = 0;  // broadcast seq of the newest staged raw sample
   bool sidecarHaveLast_ = false; // ... and it is the staging ring's newest entry
   std::atomic<bool> sidecarStale_{false};          // the daemon's heartbeat is > 3 s old
@@ -332,10 +300,8 @@ class Agent {
   // (after the daemon's layouts) at the fallback; the sampler thread then
   // continues as samplerLoop with staging pass_idx offset by passIdxBase_.
   std::vector<PassState> fallbackPasses_;
-  std::vector<PassState> retiredPasses_;  // a failed second takeover's: layouts freed at stop
   int agentIdx_ = -1;
   uint32_t passIdxBase_ = 0;
-  std::atomic<int> stepPassCount_{1};              // entries of dStepPasses_ in use
   std::atomic<bool> sidecarFellBack_{false};
   std::atomic<uint64_t> sidecarFallbackNs_{0};
   mutable std::mutex passesMu_;                    // passes_ against stats() while it changes
@@ -357,7 +323,6 @@ class Agent {
   std::atomic<uint64_t> sidecarJoins_{0};
   uint32_t sidecarIdxBase_ = 0;    // pass-table index of the daemon's layout 0
   uint32_t fallbackIdxBase_ = 0;   // ... and of this process's own pass 0 when it samples
-  uint32_t stepPassCap_ = 0;       // entries allocated in dStepPasses_
   HandBackGate handBackGate_;                      // sampler thread
   std::atomic<uint64_t> sidecarTakeovers_{0}, sidecarHandBacks_{0};
   std::atomic<bool> ctlStateChanged_{false};       // the control thread re-announces at once
@@ -465,7 +430,7 @@ class Agent {
   // pack_mode step: one event per step pack launch (recorded behind it on the
   // trainer's stream) with the staging head it packs through.  The sampler
   // reuses staging entries below the newest mark whose event has completed
-  // (stepCompleted, a host query); history(wait) waits on the newest mark.
+  // (newestCompletedPack, a host query); history(wait) waits on the newest mark.
   struct PackMark {
     hipEvent_t ev = nullptr;
     uint64_t head = 0;

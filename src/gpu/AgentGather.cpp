@@ -48,7 +48,7 @@ bool Agent::step(hipStream_t stream, std::string* err, bool catchUp) {
   // Without a gather this step (gather_mode none at world > 1, or degraded
   // after a fault), step packing still packs the staged samples into the
   // HBM ring, so the staging ring keeps draining and the history is kept.
-  auto packOnly = [&]() { return !stepPack_ || launchStepPack(stream, stepHead_.load(std::memory_order_acquire),
+  auto packOnly = [&]() { return !stepPack_ || launchStepPack(stream, stage_.head(),
                                                               nullptr, nullptr, nullptr, 0, err); };
   if (cfg_.gatherMode == "none" && cfg_.world > 1) return packOnly();
   if (gatherFailed_) return packOnly();  // degraded: keep sampling locally, never block training
@@ -79,7 +79,7 @@ bool Agent::step(hipStream_t stream, std::string* err, bool catchUp) {
   // pack_mode step: every sample staged so far is packed by this step's own
   // launch, ahead of the gather on the same stream.  pack_mode host: the
   // slots the sampler thread has published into the host ring.
-  const uint64_t head = stepPack_ ? stepHead_.load(std::memory_order_acquire)
+  const uint64_t head = stepPack_ ? stage_.head()
                                   : std::max(hostHead_.load(std::memory_order_acquire), gatheredHost_);
   if (hostPack_ && !collective_) {
     // host packing, world 1 / shm mailbox: the gather is a copy on this (the

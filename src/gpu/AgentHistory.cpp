@@ -192,8 +192,8 @@ Json Agent::history(uint64_t t0Ns, uint64_t t1Ns, uint32_t buckets, int64_t phas
   // [lo, hi): slots whose pack has completed, less what a pack running during
   // the query may overwrite once the ring has wrapped (the seq check catches
   // whatever gets through)
-  const uint64_t hi = stepPack_ ? stepCompleted() : hostHead_.load(std::memory_order_acquire);
-  const uint64_t head = std::max(hi, stepPack_ ? stepHead_.load(std::memory_order_acquire) : hi);
+  const uint64_t hi = stepPack_ ? stage_.completed() : hostHead_.load(std::memory_order_acquire);
+  const uint64_t head = std::max(hi, stepPack_ ? stage_.head() : hi);
   const uint64_t lo = std::min(hi, head > cap ? head - cap + cap / 16 : 0);
 
   if (hostPack_) {

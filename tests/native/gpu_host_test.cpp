@@ -26,6 +26,8 @@
 #include "gpu/ShmGather.h"
 #include "gpu/SlotBroadcast.h"
 #include "gpu/SlotAggregator.h"
+#include "gpu/StageRings.h"
+#include "gpu/StepPassLayout.h"
 #include "sinks/Logger.h"
 #include "testing.h"
 
@@ -1171,13 +1173,44 @@ TEST(GpuHost, SlotBroadcastMultiReader) {
   EXPECT_TRUE(SlotBroadcastReader::open(name, &err) == nullptr);
 }
 
-// pack_mode step's staging protocol (stepStageHasRoom, GatherPlan.h) under a
-// random schedule: a sampler stages entries whenever the rule allows, steps
-// launch packs of [tail, head) at random times, launches complete in order
-// after random delays (the GPU may read an entry any time before its launch
-// completes), and the sampler learns completions only through completion
-// marks.  No launch may find any entry it reads -- its range and each
-// sample's predecessor -- overwritten before it completes.
+namespace {
+// the allocator a test gives StageRings: malloc, counted against the frees
+struct CountedHeap {
+  std::atomic<int> allocs{0}, frees{0};
+  StageRings::Alloc alloc() {
+    return [this](size_t bytes) {
+      ++allocs;
+      return calloc(1, bytes);
+    };
+  }
+  StageRings::Free free() {
+    return [this](void* p) {
+      ++frees;
+      ::free(p);
+    };
+  }
+};
+// entry e as the tests stage it: its sequence number in the meta and the raw data
+void stageEntry(StageRings::Ring* r, uint64_t e) {
+  r->metaOf(e)->host_ts_ns = e;
+  r->rawOf(e)[0] = static_cast<double>(e);
+  r->rawOf(e)[1] = static_cast<double>(e) * 0.5;
+  _mm_sfence();
+}
+bool entryIntact(const StageRings::Ring* r, uint64_t e) {
+  return r->metaOf(e)->host_ts_ns == e && r->rawOf(e)[0] == static_cast<double>(e) &&
+         r->rawOf(e)[1] == static_cast<double>(e) * 0.5;
+}
+}  // namespace
+
+// pack_mode step's staging protocol (StageRings.h, the class the agent runs)
+// under a random schedule: a sampler stages entries whenever the ring has
+// room, steps launch packs of [tail, head) at random times, launches complete
+// in order after random delays (the GPU may read an entry any time before its
+// launch completes), and the sampler learns completions only through the
+// completion query.  No launch may find any entry it reads -- its range and
+// each sample's predecessor -- overwritten before it completes.  Growth is
+// off (max = start), so the long gaps do fill the ring.
 TEST(GatherPlan, StepStagingNeverOverwritesEntriesALaunchReads) {
   uint64_t rng = 0x9e3779b97f4a7c15ull;
   auto rnd = [&](uint64_t n) {
@@ -1187,20 +1220,25 @@ TEST(GatherPlan, StepStagingNeverOverwritesEntriesALaunchReads) {
     return rng % n;
   };
   for (uint64_t slots : {64ull, 256ull}) {
-    std::vector<uint64_t> ring(slots, UINT64_MAX);  // entry index -> sequence it holds
+    CountedHeap heap;
+    uint64_t done = 0;  // the completion mark the sampler queries
+    StageRings rings;
+    ASSERT_TRUE(rings.init(2, slots, slots, heap.alloc(), heap.free(), [&] { return done; }));
     struct Launch {
       uint64_t begin, end, completeAt;
     };
     std::deque<Launch> pending;
-    uint64_t head = 0, tail = 0, done = 0, dropped = 0, violations = 0, packed = 0;
+    uint64_t tail = 0, dropped = 0, violations = 0, packed = 0;
     for (uint64_t t = 0; t < 200000; ++t) {
       // the sampler: one tick
-      if (stepStageHasRoom(head, done, slots)) {
-        ring[head % slots] = head;
-        ++head;
+      uint64_t e = 0;
+      if (StageRings::Ring* r = rings.stage(&e)) {
+        stageEntry(r, e);
+        rings.publish(e);
       } else {
         ++dropped;
       }
+      const uint64_t head = rings.head();
       // a step now and then (sometimes long gaps: the ring fills)
       if (rnd(t % 5000 < 2500 ? 40 : 900) == 0 && head > tail) {
         pending.push_back({tail, head, t + 1 + rnd(300)});
@@ -1209,17 +1247,240 @@ TEST(GatherPlan, StepStagingNeverOverwritesEntriesALaunchReads) {
       // launches complete in order; each checks what it read
       while (!pending.empty() && pending.front().completeAt <= t) {
         const Launch& l = pending.front();
-        for (uint64_t e = (l.begin ? l.begin - 1 : 0); e < l.end; ++e)
-          if (ring[e % slots] != e) ++violations;
+        const auto parts = rings.parts(l.begin, l.end);
+        ASSERT_EQ(parts.size(), 1u);
+        for (uint64_t k = (l.begin ? l.begin - 1 : 0); k < l.end; ++k)
+          if (!entryIntact(parts[0].ring, k)) ++violations;
         packed += l.end - l.begin;
-        done = l.end;  // the completion mark the sampler queries
+        done = l.end;
         pending.pop_front();
       }
     }
     EXPECT_EQ(violations, 0u);
     EXPECT_TRUE(dropped > 0);          // the long gaps did fill the ring
+    EXPECT_EQ(rings.fullTicks(), dropped);
     EXPECT_TRUE(packed > 30000u);      // and the protocol kept packing
+    EXPECT_EQ(rings.grows(), 0u);
+    rings.release();
+    EXPECT_EQ(heap.allocs.load(), 1);
+    EXPECT_EQ(heap.frees.load(), 1);
   }
+}
+
+// A long pause without step(): the ring grows from 64 entries through 10
+// rings (launchStepPack kept only 8 parts and dropped the
+// newest samples).  parts() must hand every entry of [0, head) to a launch,
+// each readable in its part's ring, with its predecessor in the same ring.
+TEST(GatherPlan, StageRingsGrowThroughTenRingsWithoutAStep) {
+  CountedHeap heap;
+  StageRings rings;
+  const uint64_t maxSlots = 64ull << 9;
+  ASSERT_TRUE(rings.init(2, 64, maxSlots, heap.alloc(), heap.free(), [] { return uint64_t{0}; }));
+  uint64_t e = 0, inLast = 0;
+  while (inLast < 100) {
+    StageRings::Ring* r = rings.stage(&e);
+    ASSERT_TRUE(r != nullptr);
+    stageEntry(r, e);
+    rings.publish(e);
+    if (r->slots == maxSlots) ++inLast;
+    // more than half of this ring waits for a step: the next stage() asks for
+    // a ring twice the size (the growth thread); poll until it is taken over
+    if (r->slots < maxSlots && e + 3 - r->first > r->slots / 2) {
+      uint64_t next = 0;
+      while (rings.slots() == r->slots) {
+        ASSERT_TRUE(rings.stage(&next) != nullptr);
+        ASSERT_EQ(next, e + 1);
+        std::this_thread::yield();
+      }
+    }
+  }
+  const uint64_t head = rings.head();
+  EXPECT_EQ(head, e + 1);
+  const auto parts = rings.parts(0, head);
+  EXPECT_GT(parts.size(), 8u);
+  EXPECT_EQ(parts.size(), 10u);
+  EXPECT_EQ(rings.grows(), parts.size() - 1);
+  EXPECT_EQ(rings.slots(), maxSlots);
+  EXPECT_EQ(rings.fullTicks(), 0u);
+  EXPECT_EQ(rings.growFailures(), 0u);
+  uint64_t at = 0, intact = 0;
+  for (size_t i = 0; i < parts.size(); ++i) {
+    const auto& p = parts[i];
+    EXPECT_EQ(p.begin, at);  // contiguous, no overlap
+    EXPECT_LT(p.begin, p.end);
+    EXPECT_EQ(p.ring->slots, 64ull << i);
+    EXPECT_LE(p.end - p.begin, p.ring->slots);
+    for (uint64_t k = p.begin; k < p.end; ++k) intact += entryIntact(p.ring, k);
+    if (i > 0) {
+      EXPECT_EQ(p.ring->first, p.begin);
+      EXPECT_TRUE(entryIntact(p.ring, p.begin - 1));  // the predecessor, copied at the switch
+    }
+    at = p.end;
+  }
+  EXPECT_EQ(at, head);
+  EXPECT_EQ(intact, head);
+  // a range inside one ring, and the empty range (a payload-only launch)
+  const auto mid = rings.parts(parts[3].begin + 1, parts[5].begin + 2);
+  ASSERT_EQ(mid.size(), 3u);
+  EXPECT_EQ(mid[0].begin, parts[3].begin + 1);
+  EXPECT_EQ(mid[0].end, parts[3].end);
+  EXPECT_TRUE(mid[1].ring == parts[4].ring);
+  EXPECT_EQ(mid[2].end, parts[5].begin + 2);
+  const auto none = rings.parts(head, head);
+  ASSERT_EQ(none.size(), 1u);
+  EXPECT_TRUE(none[0].ring == parts.back().ring);
+  EXPECT_EQ(none[0].begin, head);
+  EXPECT_EQ(none[0].end, head);
+  rings.release();
+  EXPECT_EQ(heap.allocs.load(), 10);
+  EXPECT_EQ(heap.frees.load(), 10);
+}
+
+// Growth capped: a full ring refuses the entry and counts the tick; once a
+// launch has completed, its entries are staged over.
+TEST(GatherPlan, StageRingsFullRingRefusesAndCounts) {
+  CountedHeap heap;
+  uint64_t done = 0;
+  StageRings rings;
+  ASSERT_TRUE(rings.init(2, 64, 64, heap.alloc(), heap.free(), [&] { return done; }));
+  uint64_t e = 0, staged = 0;
+  auto fill = [&] {
+    while (StageRings::Ring* r = rings.stage(&e)) {
+      stageEntry(r, e);
+      rings.publish(e);
+      ++staged;
+    }
+  };
+  fill();
+  // stepStageHasRoom: head + 2 <= done + slots, so entries 0 .. 62
+  EXPECT_EQ(staged, 63u);
+  EXPECT_EQ(rings.head(), 63u);
+  EXPECT_EQ(rings.fullTicks(), 1u);
+  EXPECT_TRUE(rings.stage(&e) == nullptr);
+  EXPECT_EQ(rings.fullTicks(), 2u);
+  done = 10;  // a launch packing [0, 10) completed
+  fill();
+  EXPECT_EQ(staged, 73u);
+  EXPECT_EQ(rings.fullTicks(), 3u);
+  EXPECT_EQ(rings.completed(), 10u);
+  done = 4;  // an older mark never moves the completion back
+  EXPECT_EQ(rings.completed(), 10u);
+  EXPECT_EQ(rings.grows(), 0u);
+  EXPECT_EQ(heap.allocs.load(), 1);
+  // entry 9, the predecessor of the next launch's first sample, was kept
+  EXPECT_TRUE(entryIntact(rings.parts(10, 73)[0].ring, 9));
+}
+
+// release() frees a ring the growth thread allocated but the sampler never
+// switched to; a growth that fails is counted and staging goes on.
+TEST(GatherPlan, StageRingsReleaseFreesAGrownRingNeverSwitchedTo) {
+  CountedHeap heap;
+  StageRings rings;
+  ASSERT_TRUE(rings.init(2, 64, 128, heap.alloc(), heap.free(), [] { return uint64_t{0}; }));
+  uint64_t e = 0;
+  // entry 31 is the first with more than half of the ring (itself and a
+  // spare) unpacked: its stage() starts the growth thread, and no later
+  // stage() takes the grown ring over
+  for (int k = 0; k < 32; ++k) {
+    StageRings::Ring* r = rings.stage(&e);
+    ASSERT_TRUE(r != nullptr);
+    stageEntry(r, e);
+    rings.publish(e);
+  }
+  rings.release();  // joins the growth thread
+  EXPECT_EQ(rings.grows(), 0u);
+  EXPECT_EQ(heap.allocs.load(), 2);
+  EXPECT_EQ(heap.frees.load(), 2);
+
+  int calls = 0;
+  auto failSecond = [&](size_t bytes) { return ++calls == 1 ? calloc(1, bytes) : nullptr; };
+  ASSERT_TRUE(rings.init(2, 64, 128, failSecond, heap.free(), [] { return uint64_t{0}; }));
+  for (int k = 0; k < 32; ++k) {
+    ASSERT_TRUE(rings.stage(&e) != nullptr);
+    rings.publish(e);
+  }
+  rings.release();
+  EXPECT_EQ(rings.growFailures(), 1u);
+  EXPECT_EQ(heap.frees.load(), 3);
+}
+
+// StepPassLayout.h against the definition: for each counter c in order, the
+// ascending indices i < R with counter_of[i] == c.
+namespace {
+template <class T>
+void checkPassSegments(const std::vector<T>& counterOf, size_t R) {
+  const int C = DC_NUM_COUNTERS;
+  const PassSegments s = buildPassSegments(counterOf.data(), R);
+  ASSERT_EQ(s.segStart.size(), static_cast<size_t>(C));
+  ASSERT_EQ(s.segLen.size(), static_cast<size_t>(C));
+  std::vector<int> want;
+  for (int c = 0; c < C; ++c) {
+    EXPECT_EQ(s.segStart[static_cast<size_t>(c)], static_cast<int>(want.size()));  // exclusive prefix sum
+    for (size_t i = 0; i < R; ++i)
+      if (counterOf[i] == c) want.push_back(static_cast<int>(i));
+    EXPECT_EQ(s.segLen[static_cast<size_t>(c)], static_cast<int>(want.size()) - s.segStart[static_cast<size_t>(c)]);
+  }
+  EXPECT_TRUE(s.perm == want);
+  // every kept index exactly once
+  std::vector<int> seen(R, 0);
+  for (int i : s.perm) {
+    ASSERT_TRUE(i >= 0 && static_cast<size_t>(i) < R);
+    ++seen[static_cast<size_t>(i)];
+  }
+  for (size_t i = 0; i < R; ++i) EXPECT_EQ(seen[i], counterOf[i] >= 0 && counterOf[i] < C ? 1 : 0);
+}
+}  // namespace
+
+TEST(GpuHost, StepPassLayoutMatchesTheDefinition) {
+  checkPassSegments(std::vector<int>{}, 0);
+  checkPassSegments(std::vector<int>{DC_TCC_EA0_RDREQ}, 1);
+  // the MI355X instance counts (SQ per SE, TCC per channel, GRBM per XCD), shuffled
+  uint64_t rng = 0x2545f4914f6cdd1dull;
+  auto rnd = [&](uint64_t n) {
+    rng ^= rng << 13;
+    rng ^= rng >> 7;
+    rng ^= rng << 17;
+    return rng % n;
+  };
+  auto shuffled = [&](std::vector<int> v) {
+    for (size_t i = v.size(); i > 1; --i) std::swap(v[i - 1], v[rnd(i)]);
+    return v;
+  };
+  const int counts[DC_NUM_COUNTERS] = {32, 32, 32, 32, 32, 32, 32, 32, 128, 128, 128, 128, 8, 8};
+  std::vector<int> full, sparse, stray;
+  for (int c = 0; c < DC_NUM_COUNTERS; ++c) {
+    full.insert(full.end(), static_cast<size_t>(counts[c]), c);
+    // absent counters (a "lite" set): their segLen is 0
+    if (c % 3 != 1) sparse.insert(sparse.end(), static_cast<size_t>(counts[c]), c);
+  }
+  ASSERT_EQ(full.size(), 784u);
+  checkPassSegments(full, full.size());  // grouped already
+  full = shuffled(full);
+  checkPassSegments(full, full.size());
+  checkPassSegments(full, 100);  // R below the array's size
+  sparse = shuffled(sparse);
+  checkPassSegments(sparse, sparse.size());
+  EXPECT_EQ(buildPassSegments(sparse.data(), sparse.size()).segLen[1], 0);
+  // records of no counter (-1) and of counters outside the table are left out
+  stray = full;
+  for (size_t i = 0; i < stray.size(); i += 7) stray[i] = i % 3 == 0 ? -1 : i % 3 == 1 ? DC_NUM_COUNTERS : 1000;
+  checkPassSegments(stray, stray.size());
+  EXPECT_LT(buildPassSegments(stray.data(), stray.size()).perm.size(), stray.size());
+  // a broadcast layout: int16_t, the most raw values a broadcast carries
+  std::vector<int16_t> wide(kBroadcastMaxRaw);
+  for (auto& c : wide) c = static_cast<int16_t>(static_cast<int>(rnd(DC_NUM_COUNTERS + 2)) - 1);
+  checkPassSegments(wide, wide.size());
+  // the table entry
+  const PassSegments s = buildPassSegments(full.data(), full.size());
+  DynoAgentConsts k{};
+  k.cu_count = 256.0f;
+  const DynoStepPass p = makeStepPass(s.perm.data(), s.segStart.data(), s.segLen.data(), k, full.size(), 1, 0x3fffu);
+  EXPECT_TRUE(p.perm == s.perm.data() && p.seg_start == s.segStart.data() && p.seg_len == s.segLen.data());
+  EXPECT_EQ(p.R, 784);
+  EXPECT_EQ(p.n_counters, static_cast<int>(DC_NUM_COUNTERS));
+  EXPECT_EQ(p.pass, 1u);
+  EXPECT_EQ(p.counter_mask, 0x3fffu);
+  EXPECT_EQ(p.k.cu_count, 256.0f);
 }
 
 // a release followed at once by another hold must
