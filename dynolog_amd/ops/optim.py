@@ -165,7 +165,9 @@ class FusedAdamW(torch.optim.Optimizer):
 
 
 def adamw_reference_step(p, g, m, v, step, lr, betas, eps, wd):
-    """fp32 reference of one AdamW update (tests)."""
+    """Reference of one AdamW update in the dtype of its tensors (tests): fp32
+    for trajectories, float64 for the per-element bounds of
+    tests/ops_cases.py::ref64_adamw_step."""
     b1, b2 = betas
     p = p * (1 - lr * wd)
     m = b1 * m + (1 - b1) * g

@@ -414,7 +414,10 @@ __global__ __launch_bounds__(kBlock) void swiglu_fwd_kernel(
     const u16* __restrict__ gu, u16* __restrict__ h, int N, int F) {
   const int F8 = F / 8;
   const int total = N * F8;  // host guarantees < 2^31
-  for (int e = blockIdx.x * kBlock + threadIdx.x; e < total; e += gridDim.x * kBlock) {
+  // 64-bit counter: e + gridDim.x * kBlock may pass 2^31 on the last trip
+  for (long long e64 = (long long)blockIdx.x * kBlock + threadIdx.x; e64 < total;
+       e64 += (long long)gridDim.x * kBlock) {
+    const int e = int(e64);  // < total < 2^31: the divisions below stay 32-bit
     const int row = e / F8;
     const int c = (e - row * F8) * 8;
     const u16* gr = gu + size_t(row) * 2 * F;
@@ -432,7 +435,10 @@ __global__ __launch_bounds__(kBlock) void swiglu_bwd_kernel(
     int N, int F) {
   const int F8 = F / 8;
   const int total = N * F8;
-  for (int e = blockIdx.x * kBlock + threadIdx.x; e < total; e += gridDim.x * kBlock) {
+  // 64-bit counter: e + gridDim.x * kBlock may pass 2^31 on the last trip
+  for (long long e64 = (long long)blockIdx.x * kBlock + threadIdx.x; e64 < total;
+       e64 += (long long)gridDim.x * kBlock) {
+    const int e = int(e64);  // < total < 2^31: the divisions below stay 32-bit
     const int row = e / F8;
     const int c = (e - row * F8) * 8;
     const u16* gr = gu + size_t(row) * 2 * F;
@@ -470,7 +476,10 @@ __global__ __launch_bounds__(kBlock) void rope_kernel(
   u16* q_out = outp;
   u16* k_out = outp + size_t(T) * H * hd;
   u16* v_out = k_out + size_t(T) * KV * hd;
-  for (int e = blockIdx.x * kBlock + threadIdx.x; e < total; e += gridDim.x * kBlock) {
+  // 64-bit counter: e + gridDim.x * kBlock may pass 2^31 on the last trip
+  for (long long e64 = (long long)blockIdx.x * kBlock + threadIdx.x; e64 < total;
+       e64 += (long long)gridDim.x * kBlock) {
+    const int e = int(e64);  // < total < 2^31: the divisions below stay 32-bit
     const int th = e / CH;
     const int ch = e - th * CH;
     const int t = th / NH;
@@ -545,6 +554,7 @@ __global__ __launch_bounds__(kBlock) void xent_fwd_kernel(
 #pragma unroll
     for (int i = 1; i < 8; ++i) vm = fmaxf(vm, v[i]);
     const float mn = fmaxf(m, vm);
+    if (mn == -INFINITY) continue;  // only -inf so far (masked padding): -inf - -inf is NaN
     float acc = s * __expf(m - mn);
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc += __expf(v[i] - mn);
