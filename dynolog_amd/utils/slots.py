@@ -306,6 +306,100 @@ def history_quantiles_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, rin
     return out
 
 
+HISTORY_MAX_EPISODES = 1024
+HISTORY_MAX_RUNS = 1 << 20
+EPISODE_OPEN_BEGIN = 0x1
+EPISODE_OPEN_END = 0x2
+HISTORY_EPISODE_DTYPE = np.dtype([
+    ("first_seq", "<u8"), ("start_ns", "<u8"), ("end_ns", "<u8"), ("n_slots", "<u4"), ("flags", "<u4"),
+])
+assert HISTORY_EPISODE_DTYPE.itemsize == 32
+HISTORY_EPISODE_HEADER_DTYPE = np.dtype([
+    ("n_runs", "<u8"), ("n_episodes", "<u8"), ("total_ns", "<u8"), ("longest_ns", "<u8"), ("longest_first_seq", "<u8"),
+    ("n_eligible", "<u8"), ("n_hit", "<u8"), ("n_not_carried", "<u8"), ("returned", "<u4"), ("overflow", "<u4"),
+    ("reserved", "<u8"),
+])
+assert HISTORY_EPISODE_HEADER_DTYPE.itemsize == 80
+
+
+def history_episodes_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int,
+                               metric: int, above, thr: float, min_ns: int, max_episodes: int, max_runs: int,
+                               phase: int | None = None):
+    """The yardstick of an episode query (SlotFormat.h DynoHistoryEpisode; the
+    kernels of kernels/history.hip and the host twin historyEpisodes): (header,
+    episode header, episodes) as HISTORY_HEADER_DTYPE, HISTORY_EPISODE_HEADER_DTYPE
+    and HISTORY_EPISODE_DTYPE[returned].  Ring arguments as for history_reference
+    (the header is its header at one bucket); metric: an index into DERIVED;
+    above: false for ``v < thr``, true for ``v > thr`` in float32.  Every output
+    is an integer: implementations agree with this exactly."""
+    thr32 = np.float32(thr)
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, 1) or not 0 <= metric < len(DERIVED)
+            or np.isnan(thr32) or not 1 <= max_episodes <= HISTORY_MAX_EPISODES or not 1 <= max_runs <= HISTORY_MAX_RUNS
+            or not 0 <= min_ns < 1 << 64):
+        raise ValueError("history episode query arguments out of range")
+    assert slots.dtype == SLOT_DTYPE and len(slots) == ring_slots
+    hdr = np.zeros((), dtype=HISTORY_HEADER_DTYPE)
+    eh = np.zeros((), dtype=HISTORY_EPISODE_HEADER_DTYPE)
+    hdr["buckets"], hdr["t0_ns"], hdr["t1_ns"] = 1, t0, t1
+    seqs = np.arange(seq_lo, seq_hi, dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    if len(seqs):
+        oldest_valid = int(x["seq"][0]) == seq_lo
+        hdr["oldest_ts_ns"] = int(x["host_ts_ns"][0]) if oldest_valid else 0
+        hdr["newest_ts_ns"] = int(x["host_ts_ns"][-1]) if int(x["seq"][-1]) == seq_hi - 1 else 0
+        hdr["truncated"] = int(not oldest_valid or t0 < int(x["host_ts_ns"][0]))
+    key = np.where(x["seq"] > seqs, np.uint64(0), x["host_ts_ns"])
+    begin = seq_lo + int(np.count_nonzero(key < np.uint64(t0)))
+    end = seq_lo + int(np.count_nonzero(key < np.uint64(t1)))
+    hdr["seq_begin"], hdr["seq_end"] = begin, end
+    x, seqs = x[begin - seq_lo:end - seq_lo], seqs[begin - seq_lo:end - seq_lo]
+    ts = x["host_ts_ns"]
+    fresh = (x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1))
+    hdr["stale"] = int(np.count_nonzero(~fresh))
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    used = fresh & ((x["flags"] & SLOT_FIRST) == 0) & np.isfinite(dtf) & (dtf > 0)
+    if phase is not None:
+        used &= x["phase"] == np.uint32(phase)
+    carried = used & ((derived_mask(x["pass"]) >> metric) & 1).astype(bool)
+    v = x["derived"][:, metric]
+    eligible = carried & np.isfinite(v)
+    with np.errstate(invalid="ignore"):
+        hit = eligible & ((v > thr32) if above else (v < thr32))
+    eh["n_not_carried"] = int(np.count_nonzero(used & ~carried))
+    eh["n_eligible"] = int(np.count_nonzero(eligible))
+    eh["n_hit"] = int(np.count_nonzero(hit))
+    prev = np.concatenate([[False], hit[:-1]])
+    nxt = np.concatenate([hit[1:], [False]])
+    a = np.flatnonzero(hit & ~prev)
+    b = np.flatnonzero(hit & ~nxt)
+    eh["n_runs"] = len(a)
+    eh["overflow"] = int(len(a) > max_runs)
+    a, b = a[:max_runs], b[:max_runs]
+    d = dtf[a].astype(np.float64) * 1000.0
+    ts_a = ts[a]
+    clamp = d >= ts_a.astype(np.float64)
+    start = np.where(clamp, np.uint64(0), ts_a - np.where(clamp, 0.0, d).astype(np.uint64))
+    stop = ts[b]
+    dur = stop - start  # unsigned 64-bit
+    ep = dur >= np.uint64(min_ns)
+    eh["n_episodes"] = int(np.count_nonzero(ep))
+    out = np.zeros(int(np.count_nonzero(ep)), dtype=HISTORY_EPISODE_DTYPE)
+    out["first_seq"] = seqs[a][ep]
+    out["start_ns"] = start[ep]
+    out["end_ns"] = stop[ep]
+    out["n_slots"] = (b - a + 1)[ep]
+    out["flags"] = (np.where(seqs[a] == np.uint64(begin), EPISODE_OPEN_BEGIN, 0)
+                    | np.where(seqs[b] + np.uint64(1) == np.uint64(end), EPISODE_OPEN_END, 0))[ep]
+    if len(out):
+        durs = dur[ep]
+        eh["total_ns"] = np.sum(durs, dtype=np.uint64)  # modulo 2^64, as the unsigned sum everywhere
+        k = int(np.argmax(durs))  # the first of equal maxima
+        eh["longest_ns"], eh["longest_first_seq"] = durs[k], out["first_seq"][k]
+    out = out[:max_episodes]
+    eh["returned"] = len(out)
+    return hdr, eh, out
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

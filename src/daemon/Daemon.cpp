@@ -269,6 +269,7 @@ bool Daemon::start(std::string* err) {
     if (req.contains("phase") && req.at("phase").isString()) q["phase"] = req.at("phase");
     if (req.contains("metrics") && req.at("metrics").isArray()) q["metrics"] = req.at("metrics");
     if (req.contains("quantiles") && req.at("quantiles").isArray()) q["quantiles"] = req.at("quantiles");
+    if (req.contains("episodes") && req.at("episodes").isObject()) q["episodes"] = req.at("episodes");
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

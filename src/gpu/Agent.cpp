@@ -1540,6 +1540,9 @@ void Agent::releaseDevice() {
     freeDev(dHistQWs_);
     freeDev(dHistQ_);
     freeHost(hHistQ_);
+    freeDev(dHistEpWs_);
+    freeDev(dHistEp_);
+    freeHost(hHistEp_);
     destroyEvent(histT0_);
     destroyEvent(histT1_);
     destroyEvent(histDone_);
@@ -1765,6 +1768,7 @@ Json Agent::stats() const {
   j["history_queries"] = static_cast<unsigned long long>(historyQueries_.load());
   j["history_last_us"] = historyLastUs_.load();
   j["history_quantile_queries"] = static_cast<unsigned long long>(historyQuantileQueries_.load());
+  j["history_episode_queries"] = static_cast<unsigned long long>(historyEpisodeQueries_.load());
   j["last_error"] = lastError_;
   if (sampler_) j["agent"] = sampler_->agent().name;
   if (cfg_.isRoot()) {

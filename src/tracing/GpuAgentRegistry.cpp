@@ -285,10 +285,12 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
         return req;
       },
       timeoutMs, send);
-  // an answer too large for a datagram left its buckets in the named file
+  // an answer too large for a datagram left its buckets (an episode query: its episodes) in the named file
   for (auto& r : out["results"].asArray()) {
-    if (!r.isObject() || !r.contains("buckets_path")) continue;
-    r.asObject().erase("buckets_path");
+    if (!r.isObject()) continue;
+    const char* big = r.contains("buckets_path") ? "buckets" : r.contains("episodes_path") ? "episodes" : nullptr;
+    if (!big) continue;
+    r.asObject().erase(std::string(big) + "_path");
     const int pid = static_cast<int>(getI(r, "pid"));
     auto it = paths.find(key(pid, static_cast<int>(getI(r, "rank"))));
     if (it == paths.end()) continue;  // not a target of this request
@@ -299,9 +301,9 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
     if (!readAgentFile(p, pid, &body, &why)) {
       r["status"] = "failed: " + why;
     } else if (!Json::tryParse(body, &arr) || !arr.isArray()) {
-      r["status"] = "failed: unreadable buckets file";
+      r["status"] = std::string("failed: unreadable ") + big + " file";
     } else {
-      r["buckets"] = std::move(arr);
+      r[big] = std::move(arr);
     }
   }
   return out;
