@@ -244,6 +244,87 @@ def history_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: i
     return hdr, out
 
 
+HISTORY_MAX_PHASE_IDS = 256
+HISTORY_MAX_PHASE_NAMED = 15
+# a by-phase query's record: the same 480 bytes, the reserved word counts the group's entries
+HISTORY_PHASE_BUCKET_DTYPE = np.dtype([
+    ("first_seq", "<u8"), ("n_slots", "<u4"), ("n_reset", "<u4"), ("dt_us_sum", "<f8"), ("n_entries", "<u8"),
+    ("n", "<u4", (MAX_DERIVED,)), ("min", "<f4", (MAX_DERIVED,)), ("max", "<f4", (MAX_DERIVED,)),
+    ("wsum", "<f8", (MAX_DERIVED,)), ("w", "<f8", (MAX_DERIVED,)),
+])
+assert HISTORY_PHASE_BUCKET_DTYPE.itemsize == 480
+
+
+def history_phase_map_valid(ids, groups, n_named: int, buckets: int) -> bool:
+    """Mirror of dynoHistoryPhaseMapValid (HistoryReduce.h)."""
+    ids, groups = [int(i) for i in ids], [int(g) for g in groups]
+    return (len(ids) == len(groups) and len(ids) <= HISTORY_MAX_PHASE_IDS and 0 <= n_named <= HISTORY_MAX_PHASE_NAMED
+            and all(0 <= i < 1 << 32 for i in ids) and all(a < b for a, b in zip(ids, ids[1:]))
+            and all(0 <= g < n_named for g in groups) and buckets * (n_named + 1) <= HISTORY_MAX_BUCKETS)
+
+
+def history_by_phase_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int,
+                               buckets: int, ids, groups, n_named: int):
+    """The yardstick of a group-by-phase query (SlotFormat.h DynoHistoryPhaseMap;
+    the kernels of kernels/history.hip and the host twin historyByPhase):
+    (header, records) as HISTORY_HEADER_DTYPE and
+    HISTORY_PHASE_BUCKET_DTYPE[buckets * (n_named + 1)], record (b, g) at
+    b * (n_named + 1) + g.  Ring arguments as for history_reference, whose
+    unfiltered header this returns; ids (strictly ascending) and groups (each
+    < n_named) map a phase id to its group, every other id goes to group n_named."""
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, buckets)
+            or not history_phase_map_valid(ids, groups, n_named, buckets)):
+        raise ValueError("history by-phase query arguments out of range")
+    hdr, _ = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, buckets)
+    K, G = n_named, n_named + 1
+    R = buckets * G
+    out = np.zeros(R, dtype=HISTORY_PHASE_BUCKET_DTYPE)
+    begin, end = int(hdr["seq_begin"]), int(hdr["seq_end"])
+    seqs = np.arange(begin, end, dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts = x["host_ts_ns"]
+    fresh = (x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1))
+    ids_a, groups_a = np.asarray(ids, dtype=np.uint32), np.asarray(groups, dtype=np.int64)
+    grp = np.full(len(x), K, dtype=np.int64)
+    if len(ids_a):
+        pos = np.minimum(np.searchsorted(ids_a, x["phase"]), len(ids_a) - 1)
+        grp = np.where(ids_a[pos] == x["phase"], groups_a[pos], K)
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    used = fresh & ((x["flags"] & SLOT_FIRST) == 0) & (dtf > 0) & np.isfinite(dtf)
+    # an entry: a used slot whose predecessor in the window is not a used slot of the same group
+    same = np.zeros(len(x), dtype=bool)
+    same[1:] = used[:-1] & (grp[:-1] == grp[1:])
+    entry = used & ~same
+    # exact unsigned 64-bit bucket index: (ts - t0) * B < 2^63 by the window limit
+    b = (((np.where(fresh, ts, np.uint64(t0)) - np.uint64(t0)) * np.uint64(buckets)) // np.uint64(t1 - t0)).astype(np.int64)
+    rec = b * G + grp
+    np.add.at(out["n_slots"], rec[fresh], 1)
+    np.add.at(out["n_reset"], rec[fresh], ((x["flags"][fresh] & SLOT_RESET) != 0).astype(np.uint32))
+    first = np.full(R, np.iinfo(np.uint64).max, dtype=np.uint64)
+    np.minimum.at(first, rec[fresh], seqs[fresh])
+    out["first_seq"] = np.where(out["n_slots"] > 0, first, 0)
+    np.add.at(out["n_entries"], rec[entry], 1)
+    x, rec, dt = x[used], rec[used], dtf[used].astype(np.float64)
+    np.add.at(out["dt_us_sum"], rec, dt)
+    mask = derived_mask(x["pass"])
+    for d in range(len(DERIVED)):
+        v = x["derived"][:, d]
+        take = ((mask >> d) & 1).astype(bool) & np.isfinite(v)
+        rd, vd, wd = rec[take], v[take], dt[take]
+        n = np.zeros(R, dtype=np.uint32)
+        np.add.at(n, rd, 1)
+        mn = np.full(R, np.inf, dtype=np.float32)
+        mx = np.full(R, -np.inf, dtype=np.float32)
+        np.minimum.at(mn, rd, vd)
+        np.maximum.at(mx, rd, vd)
+        out["n"][:, d] = n
+        out["min"][:, d] = np.where(n > 0, mn, 0)
+        out["max"][:, d] = np.where(n > 0, mx, 0)
+        np.add.at(out["wsum"][:, d], rd, vd.astype(np.float64) * wd)
+        np.add.at(out["w"][:, d], rd, wd)
+    return hdr, out
+
+
 HISTORY_MAX_QUANTILES = 4
 HISTORY_QUANTILE_MAX_BUCKETS = 512
 HISTORY_QUANTILES_DTYPE = np.dtype([("q", "<f4", (MAX_DERIVED, HISTORY_MAX_QUANTILES))])

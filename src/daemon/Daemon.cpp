@@ -270,6 +270,15 @@ bool Daemon::start(std::string* err) {
     if (req.contains("metrics") && req.at("metrics").isArray()) q["metrics"] = req.at("metrics");
     if (req.contains("quantiles") && req.at("quantiles").isArray()) q["quantiles"] = req.at("quantiles");
     if (req.contains("episodes") && req.at("episodes").isObject()) q["episodes"] = req.at("episodes");
+    // "by_phase": {"depth": N, "phases": [..]}: every bucket split by phase group
+    if (req.contains("by_phase") && req.at("by_phase").isObject()) {
+      for (const char* other : {"phase", "quantiles", "episodes"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: by_phase cannot be combined with ") + other;
+          return j;
+        }
+      q["by_phase"] = req.at("by_phase");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

@@ -1541,6 +1541,7 @@ void Agent::releaseDevice() {
     freeDev(dHistQ_);
     freeHost(hHistQ_);
     freeDev(dHistEpWs_);
+    freeDev(dHistPhWs_);
     freeDev(dHistEp_);
     freeHost(hHistEp_);
     destroyEvent(histT0_);
@@ -1769,6 +1770,7 @@ Json Agent::stats() const {
   j["history_last_us"] = historyLastUs_.load();
   j["history_quantile_queries"] = static_cast<unsigned long long>(historyQuantileQueries_.load());
   j["history_episode_queries"] = static_cast<unsigned long long>(historyEpisodeQueries_.load());
+  j["history_by_phase_queries"] = static_cast<unsigned long long>(historyByPhaseQueries_.load());
   j["last_error"] = lastError_;
   if (sampler_) j["agent"] = sampler_->agent().name;
   if (cfg_.isRoot()) {

@@ -138,6 +138,7 @@ class SlotAggregator {
   void logInterval(Logger& logger, double intervalSec, uint64_t monoNowNs = 0);
 
   void setPhaseName(uint32_t id, const std::string& name) { phaseNames_[id] = name; }
+  const std::map<uint32_t, std::string>& phaseNames() const { return phaseNames_; }
   // Counters of pass `pass` (bits of delta[] positions) that were selected,
   // and of those the ones that can be read at all (the daemon reads device
   // counters from outside the workload's process, and some count only the

@@ -69,7 +69,7 @@ class GpuAgentRegistry {
   Json commTrace(const std::vector<int>& pids, int durationMs, int last, const Sender& send, int slackMs = 5000);
   // Ask every matching agent (every rank: each GPU's ring holds its own
   // history) for its slot history of a window, reduced on its GPU (IPC "gktr"
-  // op "history"; `query` carries t0_ns / t1_ns or last_s, buckets, phase, episodes,
+  // op "history"; `query` carries t0_ns / t1_ns or last_s, buckets, phase, episodes, by_phase,
   // metrics).  An answer too large for a datagram comes through the file
   // "<pathPrefix><pid>_r<rank>.json", which is read and removed.
   Json history(const std::vector<int>& pids, const Json& query, const std::string& pathPrefix, const Sender& send,
