@@ -188,7 +188,18 @@ def history_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: i
     slots: the ring image (SLOT_DTYPE[ring_slots]; seq s lives at s & (ring_slots - 1));
     [seq_lo, seq_hi) the valid range; [t0, t1) the window; phase: None = no filter.
     Defined for a ring in time order (an overwritten position, seq field > its
-    sequence number, counts as older than anything).  Sums are float64 in seq order."""
+    sequence number, counts as older than anything).  Sums are float64 in seq order.
+
+    A ring out of time order (the clock stepped back): this is still exact, and
+    the implementations agree with it, while no bucket edge, t0 or t1 lies inside
+    the stretch of time the step covers twice (the answer does not depend on the
+    slots' order then).  With an edge inside it the implementations promise only
+    this: seq_lo <= seq_begin <= seq_end <= seq_hi; every slot of [seq_begin,
+    seq_end) is in one bucket's n_slots or in `stale`; a slot is counted only in
+    the bucket of its own time stamp, so n_slots and n[d] are at most, and min /
+    max lie within, what a count slot by slot gives; and a bucket whose two edges
+    lie outside the doubled stretch equals that count exactly.  Which slots are
+    stale depends on what the edge search probes (tests/history_edge_cases.py)."""
     if not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, buckets):
         raise ValueError("history query arguments out of range")
     assert slots.dtype == SLOT_DTYPE and len(slots) == ring_slots
