@@ -328,8 +328,6 @@ void Agent::dropFailedStart() {
     comm_ = nullptr;
   }
   if (shm_) {
-    if (shmDev_) hipWarn(hipHostUnregister(shm_->base()), "hipHostUnregister mailbox");
-    shmDev_ = nullptr;
     shm_.reset();
   }
   releaseDevice();
@@ -731,11 +729,13 @@ bool Agent::openShmMailbox(const void* uid, size_t idLen, std::string* err) {
     shm_.reset();
     return false;
   }
-  if (!root) {
-    // the step pack kernel writes this rank's block straight into the mailbox
-    // (host packing copies it in on the trainer's thread)
-    HIP_OK(hipHostRegister(shm_->base(), shm_->bytes(), hipHostRegisterMapped), "hipHostRegister mailbox");
-    HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&shmDev_), shm_->base(), 0), "mailbox device ptr");
+  if (!root && stepPack_) {
+    // the step pack kernel writes this rank's block into pinned memory of this
+    // process, one block per mailbox entry, copied into the mailbox when it is
+    // published (host packing copies it in on the trainer's thread)
+    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&shmStage_), static_cast<size_t>(shm_->entries()) * sendBytes_,
+                         hipHostMallocCoherent),
+           "hipHostMalloc mailbox blocks");
   }
   shmEnq_ = 0;
   shmPending_.clear();
@@ -1478,8 +1478,6 @@ void Agent::stop() {
     comm_ = nullptr;
   }
   if (shm_) {
-    if (shmDev_) hipWarn(hipHostUnregister(shm_->base()), "hipHostUnregister mailbox");
-    shmDev_ = nullptr;
     shm_.reset();  // rank 0 unlinks the segment
   }
   releaseDevice();
@@ -1525,6 +1523,7 @@ void Agent::releaseDevice() {
     recvPending_[i] = false;
   }
   recvNext_ = 0;
+  freeHost(shmStage_);
   {
     std::lock_guard<std::mutex> g(packMu_);
     for (auto& m : packMarks_) {

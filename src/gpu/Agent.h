@@ -506,16 +506,20 @@ class Agent {
   // into a shared-memory mailbox that rank 0's consumer drains
   bool shmMode_ = false;
   std::unique_ptr<ShmGather> shm_;
-  uint8_t* shmDev_ = nullptr;      // device pointer of the registered segment (ranks > 0)
+  // pack_mode step, ranks > 0: pinned blocks the pack kernel writes, one per
+  // mailbox entry; a completed block is copied into the mailbox, then published
+  uint8_t* shmStage_ = nullptr;
   uint64_t shmEnq_ = 0;            // payloads handed to the mailbox (stepMu_)
   std::atomic<uint64_t> shmFull_{0};  // steps whose payload waited for a full mailbox
   bool drainShm();                 // rank 0 consumer: ingest every published peer block
   struct ShmPending {
     int slot;                      // gathered_[slot] fires when the block has landed
     uint64_t count;                // the lane's pub value once it has
+    const uint8_t* staged;         // the pinned block the kernel wrote
+    uint8_t* blk;                  // its mailbox block
   };
   std::deque<ShmPending> shmPending_;  // ranks > 0: written, not yet published (stepMu_)
-  bool shmDefer(hipStream_t stream, std::string* err);
+  bool shmDefer(hipStream_t stream, const uint8_t* staged, uint8_t* blk, std::string* err);
   void shmPublishCompleted(bool wait, uint64_t upTo = ~0ull);
   std::mutex stepMu_;
 

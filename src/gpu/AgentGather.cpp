@@ -201,7 +201,7 @@ void Agent::hostGatherLocal(uint64_t head) {
 // and at stop().  No host callback and no second stream: a stream waiting on
 // the trainer's event slows the trainer's kernels (gatherCollective).  The
 // peer's payload reaches rank 0 a step later, well inside the log interval.
-bool Agent::shmDefer(hipStream_t stream, std::string* err) {
+bool Agent::shmDefer(hipStream_t stream, const uint8_t* staged, uint8_t* blk, std::string* err) {
   shmPublishCompleted(false);
   if (shmPending_.size() >= static_cast<size_t>(kRecv)) {
     // kRecv payloads still in flight: the GPU is that far behind the host;
@@ -211,7 +211,7 @@ bool Agent::shmDefer(hipStream_t stream, std::string* err) {
   const int slot = recvNext_;
   recvNext_ = (recvNext_ + 1) % kRecv;
   HIP_OK(hipEventRecord(gathered_[slot], stream), "record gathered");
-  shmPending_.push_back({slot, ++shmEnq_});
+  shmPending_.push_back({slot, ++shmEnq_, staged, blk});
   return true;
 }
 
@@ -224,6 +224,9 @@ void Agent::shmPublishCompleted(bool wait, uint64_t upTo) {
       q = hipEventSynchronize(gathered_[p.slot]);
     }
     if (q != hipSuccess) hipWarn(q, "shm payload event");  // publish anyway: rank 0 checks the block's rank
+    // pinned block -> mailbox block: the header and the slots it counts
+    const uint32_t n = reinterpret_cast<const DynoGatherHeader*>(p.staged)->count;
+    memcpy(p.blk, p.staged, gatherBlockBytes(std::min(n, cfg_.gatherCapSlots)));
     shm_->publish(cfg_.rank, p.count);
     shmPending_.pop_front();
   }
@@ -231,7 +234,9 @@ void Agent::shmPublishCompleted(bool wait, uint64_t upTo) {
 
 // pack_mode step, world 1 (or the shm mailbox): the step's pack launch also
 // writes the payload -- straight into the consumer's pinned buffer at world 1
-// (the drain), into this rank's mailbox block on a shm peer.
+// (the drain), into a pinned block of its own on a shm peer, which copies it
+// into its mailbox block when it publishes (the mailbox segment itself is not
+// registered with the GPU: not every machine can pin memory it did not allocate).
 bool Agent::stepGatherLocal(hipStream_t stream, uint64_t head, std::string* err) {
   const auto rg = planGatherRange(head, gatheredHost_, cfg_.gatherCapSlots, cfg_.ringSlots);
   const DynoGatherHeader gh = makeGatherHeader(rg, head, cfg_.gatherCapSlots, cfg_.rank, cfg_.device, pciLoc_);
@@ -242,9 +247,10 @@ bool Agent::stepGatherLocal(hipStream_t stream, uint64_t head, std::string* err)
       shmFull_++;  // rank 0 is behind: pack only, the slots wait in the HBM ring
       return launchStepPack(stream, head, nullptr, nullptr, nullptr, 0, err);
     }
-    uint8_t* dev = shmDev_ + (blk - static_cast<uint8_t*>(shm_->base()));
-    if (!launchStepPack(stream, head, dev, &gh, nullptr, 0, err)) return false;
-    if (!shmDefer(stream, err)) return false;
+    // (block k is free again once payload k - entries was consumed, so published and copied)
+    uint8_t* staged = shmStage_ + (shmEnq_ % static_cast<uint64_t>(shm_->entries())) * sendBytes_;
+    if (!launchStepPack(stream, head, staged, &gh, nullptr, 0, err)) return false;
+    if (!shmDefer(stream, staged, blk, err)) return false;
     commitGather(rg);
     return true;
   }

@@ -119,7 +119,20 @@ std::vector<KfdProcess> kfdProcesses(const std::string& kfdRoot) {
   return out;
 }
 
-LocalGpuProcess localGpuProcess(int pid, const std::string& procRoot) {
+namespace {
+// "/dev/dri/renderD128" -> the BDF its sysfs entry's device link ends in
+// (<drmRoot>/renderD128/device -> ../../../0000:8e:00.0), or ""
+std::string renderNodeBdf(const std::string& node, const std::string& drmRoot) {
+  char buf[512];
+  const ssize_t n = readlink((drmRoot + node.substr(node.rfind('/')) + "/device").c_str(), buf, sizeof(buf) - 1);
+  if (n <= 0) return "";
+  buf[n] = 0;
+  const char* slash = strrchr(buf, '/');
+  return slash ? slash + 1 : buf;
+}
+}  // namespace
+
+LocalGpuProcess localGpuProcess(int pid, const std::string& procRoot, const std::string& drmRoot) {
   LocalGpuProcess lp;
   lp.pid = pid;
   const std::string p = std::to_string(pid);
@@ -145,16 +158,22 @@ LocalGpuProcess localGpuProcess(int pid, const std::string& procRoot) {
         kib = std::strtoull(line.c_str() + 15, nullptr, 10);
       }
     }
-    if (!pdev.empty()) lp.vramKiB[pdev] += kib;
+    if (!pdev.empty()) {
+      lp.vramKiB[pdev] += kib;
+    } else if (!(pdev = renderNodeBdf(buf, drmRoot)).empty()) {
+      // an fdinfo without the DRM keys: the GPU from sysfs, no memory figure
+      lp.vramKiB[pdev] += 0;
+      lp.vramUnknown.insert(pdev);
+    }
   }
   return lp;
 }
 
-std::vector<LocalGpuProcess> localGpuProcesses(const std::string& procRoot) {
+std::vector<LocalGpuProcess> localGpuProcesses(const std::string& procRoot, const std::string& drmRoot) {
   std::vector<LocalGpuProcess> out;
   for (const auto& p : listDir(procRoot)) {
     if (!allDigits(p)) continue;
-    LocalGpuProcess lp = localGpuProcess(atoi(p.c_str()), procRoot);
+    LocalGpuProcess lp = localGpuProcess(atoi(p.c_str()), procRoot, drmRoot);
     if (lp.kfd || !lp.vramKiB.empty()) out.push_back(std::move(lp));
   }
   return out;
@@ -211,7 +230,7 @@ ProcScanCache::Entry& ProcScanCache::entry(int pid, uint64_t nowNs) {
 const LocalGpuProcess& ProcScanCache::local(int pid, uint64_t nowNs) {
   Entry& e = entry(pid, nowNs);
   if (!e.haveLocal || nowNs - e.localNs > ttlNs_) {
-    LocalGpuProcess lp = localGpuProcess(pid, procRoot_);
+    LocalGpuProcess lp = localGpuProcess(pid, procRoot_, drmRoot_);
     if (!lp.vramKiB.empty()) {
       e.vramNs = nowNs;
       e.departNs = 0;
@@ -249,13 +268,13 @@ bool ProcScanCache::countable(int pid, uint64_t gpuId, uint64_t nowNs) {
 
 const std::vector<LocalGpuProcess>& ProcScanCache::all(uint64_t nowNs) {
   if (!haveAll_ || nowNs - allNs_ > ttlNs_) {
-    all_ = localGpuProcesses(procRoot_);
+    all_ = localGpuProcesses(procRoot_, drmRoot_);
     allNs_ = nowNs;
     haveAll_ = true;
     ++reads_;
     for (const auto& lp : all_) {
       for (const auto& kv : lp.vramKiB) {
-        if (kv.second < kMinStandInVramKiB || !lp.kfd) continue;  // as for a stand-in
+        if (!lp.holds(kv.first, kMinStandInVramKiB) || !lp.kfd) continue;  // as for a stand-in
         auto& h = heldVram_[lp.pid];
         h.first = nowNs;
         h.second.insert(kv.first);
@@ -272,8 +291,7 @@ int ProcScanCache::departingStandIns(const std::string& bdf, uint64_t nowNs) con
   for (const auto& [pid, h] : heldVram_) {
     if (nowNs - h.first > kDepartingGraceNs || !h.second.count(bdf)) continue;
     const bool holdsNow = std::any_of(all_.begin(), all_.end(), [&, p = pid](const LocalGpuProcess& lp) {
-      const auto vr = lp.vramKiB.find(bdf);
-      return lp.pid == p && lp.kfd && vr != lp.vramKiB.end() && vr->second >= kMinStandInVramKiB;
+      return lp.pid == p && lp.kfd && lp.holds(bdf, kMinStandInVramKiB);
     });
     if (!holdsNow) ++n;
   }
@@ -308,13 +326,12 @@ GpuVisibility visibilityOf(uint64_t gpuId, const std::string& bdf, int selfPid, 
   int standIns = 0;
   bool selfHere = false;
   for (const auto& lp : localsFn()) {
-    auto vr = lp.vramKiB.find(bdf);
-    if (vr == lp.vramKiB.end() || !lp.kfd) continue;
+    if (!lp.vramKiB.count(bdf) || !lp.kfd) continue;
     if (lp.pid == selfPid) {
       selfHere = true;
       continue;
     }
-    if (seen.count(lp.pid) || vr->second < kMinStandInVramKiB) continue;
+    if (seen.count(lp.pid) || !lp.holds(bdf, kMinStandInVramKiB)) continue;
     ++standIns;
     v.pids.push_back(lp.pid);
     if (!countableOf(lp.pid)) v.uncountable.push_back(lp.pid);
@@ -322,7 +339,41 @@ GpuVisibility visibilityOf(uint64_t gpuId, const std::string& bdf, int selfPid, 
   v.foreign = std::max(0, rest - standIns - (selfHere ? 1 : 0) - departedStandIns());
   return v;
 }
+
+// KFD lists no processes: the local compute processes on the GPU are all
+// there is to go by (a stand-in's test: the GPU open, and memory on it
+// wherever fdinfo says how much)
+template <typename CountableFn>
+GpuVisibility visibilityOfLocals(const std::string& bdf, int selfPid, const std::vector<LocalGpuProcess>& locals,
+                                 CountableFn&& countableOf) {
+  GpuVisibility v;
+  v.known = true;
+  for (const auto& lp : locals) {
+    if (lp.pid == selfPid || !lp.kfd || !lp.holds(bdf, kMinStandInVramKiB)) continue;
+    v.pids.push_back(lp.pid);
+    if (!countableOf(lp.pid)) v.uncountable.push_back(lp.pid);
+  }
+  return v;
+}
 }  // namespace
+
+KfdView kfdView(const std::string& kfdRoot) {
+  for (const char* sub : {"/proc", ""})
+    if (DIR* d = opendir((kfdRoot + sub).c_str())) {
+      closedir(d);
+      return *sub ? KfdView::ProcessList : KfdView::NoProcessList;
+    }
+  return KfdView::None;
+}
+
+GpuVisibility localVisibility(uint64_t gpuId, const std::string& bdf, int selfPid,
+                              const std::vector<LocalGpuProcess>& locals, const std::string& procRoot) {
+  return visibilityOfLocals(bdf, selfPid, locals, [&](int pid) { return processCountable(pid, gpuId, procRoot); });
+}
+
+GpuVisibility localVisibility(uint64_t gpuId, const std::string& bdf, int selfPid, ProcScanCache& cache, uint64_t nowNs) {
+  return visibilityOfLocals(bdf, selfPid, cache.all(nowNs), [&](int pid) { return cache.countable(pid, gpuId, nowNs); });
+}
 
 GpuVisibility gpuVisibility(uint64_t gpuId, const std::string& bdf, int selfPid, const std::vector<KfdProcess>& procs,
                             ProcScanCache& cache, uint64_t nowNs) {
@@ -349,16 +400,15 @@ GpuVisibility gpuVisibility(uint64_t gpuId, const std::string& bdf, int selfPid,
 }
 
 GpuVisibility gpuVisibility(uint64_t gpuId, const std::string& bdf, int selfPid, const std::string& kfdRoot,
-                            const std::string& procRoot) {
-  if (DIR* d = opendir((kfdRoot + "/proc").c_str())) {
-    closedir(d);
-  } else {
-    return GpuVisibility{};
-  }
+                            const std::string& procRoot, const std::string& drmRoot) {
+  const KfdView view = kfdView(kfdRoot);
+  if (view == KfdView::None) return GpuVisibility{};
+  if (view == KfdView::NoProcessList)
+    return localVisibility(gpuId, bdf, selfPid, localGpuProcesses(procRoot, drmRoot), procRoot);
   std::vector<LocalGpuProcess> locals;
   bool scanned = false;
   auto fn = [&]() -> const std::vector<LocalGpuProcess>& {
-    if (!scanned) locals = localGpuProcesses(procRoot);
+    if (!scanned) locals = localGpuProcesses(procRoot, drmRoot);
     scanned = true;
     return locals;
   };

@@ -236,7 +236,7 @@ bool DeviceMonitor::start(const Json& cfg, std::unique_ptr<CounterBackend> backe
   }
   // the first visibility check before any sample: the first interval is
   // already sampled and logged with the right set and masks
-  procCache_ = std::make_unique<ProcScanCache>(procRoot_);
+  procCache_ = std::make_unique<ProcScanCache>(procRoot_, 2'000'000'000ull, sysRoot_ + "/sys/class/drm");
   checkVisibility(monoNs());
   for (auto& g : gpus_) {
     std::lock_guard<std::mutex> lk(g->mu);
@@ -295,16 +295,15 @@ void DeviceMonitor::applyMasks(Gpu* g) {
 // state comes from the cache (the GPU threads never touch /proc).
 void DeviceMonitor::checkVisibility(uint64_t nowNs) {
   std::vector<KfdProcess> procs;
-  bool known = false;
-  if (DIR* d = opendir((kfdRoot_ + "/proc").c_str())) {
-    closedir(d);
-    procs = kfdProcesses(kfdRoot_);
-    known = true;
-  }
+  const KfdView view = kfdView(kfdRoot_);
+  if (view == KfdView::ProcessList) procs = kfdProcesses(kfdRoot_);
+  const int self = static_cast<int>(getpid());
   for (auto& gp : gpus_) {
     Gpu* g = gp.get();
     GpuVisibility v;
-    if (known) v = gpuVisibility(g->gpuId, pciLocString(g->pciLoc), static_cast<int>(getpid()), procs, *procCache_, nowNs);
+    if (view == KfdView::ProcessList) v = gpuVisibility(g->gpuId, pciLocString(g->pciLoc), self, procs, *procCache_, nowNs);
+    // a KFD that lists no processes: the local /proc scan is all there is
+    else if (view == KfdView::NoProcessList) v = localVisibility(g->gpuId, pciLocString(g->pciLoc), self, *procCache_, nowNs);
     const bool limited = !v.full();
     std::lock_guard<std::mutex> lk(g->mu);
     g->vis = v;

@@ -12,9 +12,9 @@
 // cons (release).  A writer never waits: when its lane is full (rank 0 has
 // fallen `entries` payloads behind) the payload is dropped and counted.
 // Single producer / single consumer per lane, host-only; the GPU writes a
-// block through a device pointer of the registered segment and the producer
-// publishes it from its next step() (or flush / stop) once the event recorded
-// after that write has fired (Agent::shmDefer).
+// block into pinned memory of the producer's own, and the producer copies it
+// into the segment and publishes it from its next step() (or flush / stop)
+// once the event recorded after that write has fired (Agent::shmDefer).
 #pragma once
 
 #include <atomic>

@@ -1022,6 +1022,65 @@ TEST(GpuHost, DdpPeerBuffersKeepTheFullSetWhenMarkedOnEveryGpu) {
   EXPECT_TRUE(gpuVisibility(777, kBdfB, 400, t.root + "/kfd", t.root + "/proc").full());
 }
 
+// A guest whose KFD lists no processes (no kfd/proc) and whose fdinfo has no
+// DRM keys: the GPU's compute processes are the local ones with /dev/kfd and
+// the GPU's render node open, the node's BDF from its sysfs device link.
+TEST(GpuHost, VisibilityWithoutKfdProcessListOrDrmFdinfo) {
+  FakeTree t;
+  t.put("kfd/topology/nodes/1/gpu_id", "12657\n");  // KFD is there; kfd/proc is not
+  t.link("drm/renderD128/device", "../../../0000:75:00.0");
+  t.link("drm/renderD129/device", "../../../0000:05:00.0");
+  auto bare = [&](int pid, const char* node, const std::string& maps, bool kfd = true) {
+    const std::string p = "proc/" + std::to_string(pid);
+    if (kfd) t.link(p + "/fd/3", "/dev/kfd");
+    t.link(p + "/fd/7", node);
+    t.put(p + "/fdinfo/7", "pos:\t0\nflags:\t02100002\nmnt_id:\t24\nino:\t135\n");
+    t.put(p + "/maps", maps);
+  };
+  bare(100, "/dev/dri/renderD128", "7f40-7f41 r--s 0 00:01 9 /memfd:dynolog-countable:12657 (deleted)\n");
+  bare(300, "/dev/dri/renderD129", "");       // a plain job on the other GPU
+  bare(400, "/dev/dri/renderD128", "");       // the daemon
+  bare(500, "/dev/dri/renderD128", "", false);  // a render client, no compute
+  const std::string kfd = t.root + "/kfd", proc = t.root + "/proc", drm = t.root + "/drm";
+  EXPECT_TRUE(kfdView(kfd) == KfdView::NoProcessList);
+  EXPECT_TRUE(kfdView(t.root + "/nokfd") == KfdView::None);
+  auto lp = localGpuProcess(100, proc, drm);
+  EXPECT_TRUE(lp.kfd);
+  EXPECT_EQ(lp.vramKiB.count(kBdfA), 1u);
+  EXPECT_TRUE(lp.holds(kBdfA, 512));  // open, no figure to go by
+  EXPECT_FALSE(lp.holds(kBdfB, 0));
+  auto v = gpuVisibility(12657, kBdfA, 400, kfd, proc, drm);
+  EXPECT_TRUE(v.known);
+  ASSERT_EQ(v.pids.size(), 1u);
+  EXPECT_EQ(v.pids[0], 100);
+  EXPECT_EQ(v.foreign, 0);
+  EXPECT_TRUE(v.full());
+  // a plain job joins the GPU: limited, by its pid
+  bare(200, "/dev/dri/renderD128", "7f00-7f10 r-xp 0 08:01 1 /opt/x/libamdhip64.so\n");
+  v = gpuVisibility(12657, kBdfA, 400, kfd, proc, drm);
+  EXPECT_EQ(v.pids.size(), 2u);
+  ASSERT_EQ(v.uncountable.size(), 1u);
+  EXPECT_EQ(v.uncountable[0], 200);
+  EXPECT_FALSE(v.full());
+  v = gpuVisibility(999, kBdfB, 400, kfd, proc, drm);
+  ASSERT_EQ(v.uncountable.size(), 1u);
+  EXPECT_EQ(v.uncountable[0], 300);
+  // the daemon's cached check agrees, and drops the job once it is gone
+  const uint64_t s = 1'000'000'000ull;
+  ProcScanCache cache(proc, 1 * s, drm);
+  v = localVisibility(12657, kBdfA, 400, cache, 10 * s);
+  ASSERT_EQ(v.uncountable.size(), 1u);
+  EXPECT_EQ(v.uncountable[0], 200);
+  std::string rm = "rm -rf " + proc + "/200";
+  ASSERT_EQ(system(rm.c_str()), 0);
+  EXPECT_TRUE(localVisibility(12657, kBdfA, 400, cache, 12 * s).full());
+  // an fdinfo that says how much: the runtime up and nothing launched is no compute process
+  t.proc(600, kBdfA, 44, "");
+  EXPECT_TRUE(gpuVisibility(12657, kBdfA, 400, kfd, proc, drm).full());
+  t.proc(600, kBdfA, 4096, "");
+  EXPECT_FALSE(gpuVisibility(12657, kBdfA, 400, kfd, proc, drm).full());
+}
+
 TEST(GpuHost, CountableMarkIsSeenInOwnMaps) {
   EXPECT_TRUE(dynoMarkCountable({42, 4242}));
   EXPECT_TRUE(processCountable(static_cast<int>(getpid()), 4242));
