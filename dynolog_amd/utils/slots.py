@@ -492,6 +492,136 @@ def history_episodes_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring
     return hdr, eh, out
 
 
+HISTORY_FOLD_MAX_BINS = 1024
+HISTORY_FOLD_MAX_PERIODS = 1 << 20
+HISTORY_FOLD_MAX_LISTED = 1024
+PERIOD_KEPT = 0x1
+HISTORY_PERIOD_DTYPE = np.dtype([
+    ("first_seq", "<u8"), ("start_ns", "<u8"), ("length_ns", "<u8"), ("n_slots", "<u4"), ("flags", "<u4"),
+])
+assert HISTORY_PERIOD_DTYPE.itemsize == 32
+HISTORY_FOLD_HEADER_DTYPE = np.dtype([
+    ("n_entries", "<u8"), ("n_periods", "<u8"), ("n_kept", "<u8"), ("total_ns", "<u8"), ("shortest_ns", "<u8"),
+    ("shortest_first_seq", "<u8"), ("longest_ns", "<u8"), ("longest_first_seq", "<u8"), ("bin_ns", "<u8"),
+    ("n_folded", "<u8"), ("n_beyond", "<u8"), ("n_misplaced", "<u8"), ("n_outside", "<u8"),
+    ("bins", "<u4"), ("returned", "<u4"), ("overflow", "<u4"), ("reserved", "<u4"), ("reserved2", "<u8"),
+])
+assert HISTORY_FOLD_HEADER_DTYPE.itemsize == 128
+# a fold query's record: the same 480 bytes, the reserved word counts the kept periods that reach the bin
+HISTORY_FOLD_BUCKET_DTYPE = np.dtype([
+    ("first_seq", "<u8"), ("n_slots", "<u4"), ("n_reset", "<u4"), ("dt_us_sum", "<f8"), ("n_periods", "<u8"),
+    ("n", "<u4", (MAX_DERIVED,)), ("min", "<f4", (MAX_DERIVED,)), ("max", "<f4", (MAX_DERIVED,)),
+    ("wsum", "<f8", (MAX_DERIVED,)), ("w", "<f8", (MAX_DERIVED,)),
+])
+assert HISTORY_FOLD_BUCKET_DTYPE.itemsize == 480
+
+
+def history_fold_args_valid(ids, bins: int, bin_ns: int, min_ns: int, max_ns: int, max_periods: int,
+                            max_listed: int) -> bool:
+    """Mirror of dynoHistoryFoldArgsValid (HistoryReduce.h)."""
+    ids = [int(i) for i in ids]
+    return (1 <= len(ids) <= HISTORY_MAX_PHASE_IDS and all(0 <= i < 1 << 32 for i in ids)
+            and all(a < b for a, b in zip(ids, ids[1:])) and 1 <= bins <= HISTORY_FOLD_MAX_BINS
+            and 0 <= bin_ns < HISTORY_MAX_WINDOW_NS and 0 <= min_ns < 1 << 64 and 0 <= max_ns < 1 << 64
+            and (max_ns == 0 or min_ns <= max_ns) and 1 <= max_periods <= HISTORY_FOLD_MAX_PERIODS
+            and 1 <= max_listed <= HISTORY_FOLD_MAX_LISTED)
+
+
+def history_fold_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int, ids,
+                           bins: int, bin_ns: int = 0, min_ns: int = 0, max_ns: int = 0, max_periods: int = 256,
+                           max_listed: int = 256):
+    """The yardstick of a fold query (SlotFormat.h DynoHistoryFoldHeader; the
+    kernels of kernels/history.hip and the host twin historyFold): (header, fold
+    header, records, periods) as HISTORY_HEADER_DTYPE, HISTORY_FOLD_HEADER_DTYPE,
+    HISTORY_FOLD_BUCKET_DTYPE[bins] and HISTORY_PERIOD_DTYPE[returned].  Ring
+    arguments as for history_reference (the header is its header at one bucket);
+    ids: the anchor phase ids, strictly ascending.  Plain NumPy and Python
+    integers; the float64 sums run in sequence order."""
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, 1)
+            or not history_fold_args_valid(ids, bins, bin_ns, min_ns, max_ns, max_periods, max_listed)):
+        raise ValueError("history fold query arguments out of range")
+    hdr, whole = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, 1)
+    fh = np.zeros((), dtype=HISTORY_FOLD_HEADER_DTYPE)
+    out = np.zeros(bins, dtype=HISTORY_FOLD_BUCKET_DTYPE)
+    fh["bins"] = bins
+    begin, end = int(hdr["seq_begin"]), int(hdr["seq_end"])
+    seqs = np.arange(begin, end, dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts = x["host_ts_ns"]
+    fresh = (x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1))
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    used = fresh & ((x["flags"] & SLOT_FIRST) == 0) & (dtf > 0) & np.isfinite(dtf)
+    anchor = used & np.isin(x["phase"], np.asarray([int(i) for i in ids], dtype=np.uint32))
+    is_entry = np.zeros(len(x), dtype=bool)
+    is_entry[1:] = anchor[1:] & ~anchor[:-1]
+    e = np.flatnonzero(is_entry)  # offsets from seq_begin
+    fh["n_entries"] = len(e)
+    n_all = max(len(e) - 1, 0)
+    P = min(n_all, max_periods)
+    fh["n_periods"], fh["overflow"] = P, int(n_all > max_periods)
+    per = np.zeros(P, dtype=HISTORY_PERIOD_DTYPE)
+    kept_len = [0] * P
+    for k in range(P):
+        tk, tn = int(ts[e[k]]), int(ts[e[k + 1]])
+        length = tn - tk if tn > tk else 0
+        kept = length > 0 and length >= min_ns and (max_ns == 0 or length <= max_ns)
+        per[k] = (begin + int(e[k]), tk, length, int(e[k + 1] - e[k]), PERIOD_KEPT if kept else 0)
+        kept_len[k] = length if kept else 0
+    kept = [k for k in range(P) if kept_len[k]]
+    fh["n_kept"] = len(kept)
+    if kept:
+        lens = [kept_len[k] for k in kept]
+        fh["total_ns"] = sum(lens) % (1 << 64)
+        ks, kl = kept[lens.index(min(lens))], kept[lens.index(max(lens))]  # the first of equal extremes
+        fh["shortest_ns"], fh["shortest_first_seq"] = kept_len[ks], per["first_seq"][ks]
+        fh["longest_ns"], fh["longest_first_seq"] = kept_len[kl], per["first_seq"][kl]
+    width = bin_ns if bin_ns > 0 else max(1, -(-int(fh["longest_ns"]) // bins))
+    fh["bin_ns"] = width
+    out["n_periods"] = [sum(1 for k in kept if kept_len[k] > j * width) for j in range(bins)]
+    mn = np.full((bins, MAX_DERIVED), np.inf, dtype=np.float32)
+    mx = np.full((bins, MAX_DERIVED), -np.inf, dtype=np.float32)
+    carried = ((derived_mask(x["pass"])[:, None] >> np.arange(MAX_DERIVED)) & 1).astype(bool)
+    carried[:, len(DERIVED):] = False
+    in_kept = folded = beyond = misplaced = 0
+    for k in kept:
+        tk = int(ts[e[k]])
+        for i in range(int(e[k]), int(e[k + 1])):
+            if not fresh[i]:
+                continue
+            in_kept += 1
+            t = int(ts[i])
+            if t < tk or t >= tk + kept_len[k]:
+                misplaced += 1
+                continue
+            j = (t - tk) // width
+            if j >= bins:
+                beyond += 1
+                continue
+            folded += 1
+            b = out[j]
+            if b["n_slots"] == 0:
+                b["first_seq"] = seqs[i]
+            b["n_slots"] += 1
+            b["n_reset"] += int((x["flags"][i] & SLOT_RESET) != 0)
+            if not used[i]:
+                continue
+            dt = np.float64(dtf[i])
+            b["dt_us_sum"] += dt
+            v = x["derived"][i]
+            take = carried[i] & np.isfinite(v)  # per metric; every (bin, metric) sum stays in sequence order
+            b["n"][take] += 1
+            mn[j, take], mx[j, take] = np.minimum(mn[j, take], v[take]), np.maximum(mx[j, take], v[take])
+            b["wsum"][take] += v[take].astype(np.float64) * dt
+            b["w"][take] += dt
+    out["min"] = np.where(out["n"] > 0, mn, 0)
+    out["max"] = np.where(out["n"] > 0, mx, 0)
+    fh["n_folded"], fh["n_beyond"], fh["n_misplaced"] = folded, beyond, misplaced
+    fh["n_outside"] = int(whole["n_slots"][0]) - in_kept
+    per = per[:max_listed]
+    fh["returned"] = len(per)
+    return hdr, fh, out, per
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

@@ -279,6 +279,15 @@ bool Daemon::start(std::string* err) {
         }
       q["by_phase"] = req.at("by_phase");
     }
+    // "fold": {"anchor", "bins", "bin_ms", "min_ms", "max_ms", "max"}: the ring folded on a phase into a step profile
+    if (req.contains("fold") && req.at("fold").isObject()) {
+      for (const char* other : {"phase", "by_phase", "episodes", "quantiles", "buckets"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: fold cannot be combined with ") + other;
+          return j;
+        }
+      q["fold"] = req.at("fold");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

@@ -1541,6 +1541,9 @@ void Agent::releaseDevice() {
     freeHost(hHistQ_);
     freeDev(dHistEpWs_);
     freeDev(dHistPhWs_);
+    freeDev(dHistFoldWs_);
+    freeDev(dHistFold_);
+    freeHost(hHistFold_);
     freeDev(dHistEp_);
     freeHost(hHistEp_);
     destroyEvent(histT0_);
@@ -1770,6 +1773,7 @@ Json Agent::stats() const {
   j["history_quantile_queries"] = static_cast<unsigned long long>(historyQuantileQueries_.load());
   j["history_episode_queries"] = static_cast<unsigned long long>(historyEpisodeQueries_.load());
   j["history_by_phase_queries"] = static_cast<unsigned long long>(historyByPhaseQueries_.load());
+  j["history_fold_queries"] = static_cast<unsigned long long>(historyFoldQueries_.load());
   j["last_error"] = lastError_;
   if (sampler_) j["agent"] = sampler_->agent().name;
   if (cfg_.isRoot()) {

@@ -285,10 +285,14 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
         return req;
       },
       timeoutMs, send);
-  // an answer too large for a datagram left its buckets (an episode query: its episodes) in the named file
+  // an answer too large for a datagram left its buckets (an episode query: its episodes, a fold: its
+  // profile) in the named file
   for (auto& r : out["results"].asArray()) {
     if (!r.isObject()) continue;
-    const char* big = r.contains("buckets_path") ? "buckets" : r.contains("episodes_path") ? "episodes" : nullptr;
+    const char* big = r.contains("buckets_path")    ? "buckets"
+                      : r.contains("episodes_path") ? "episodes"
+                      : r.contains("profile_path")  ? "profile"
+                                                    : nullptr;
     if (!big) continue;
     r.asObject().erase(std::string(big) + "_path");
     const int pid = static_cast<int>(getI(r, "pid"));
