@@ -622,6 +622,87 @@ def history_fold_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slo
     return hdr, fh, out, per
 
 
+HISTORY_JOINT_MAX_BINS = 64
+HISTORY_JOINT_CELL_DTYPE = np.dtype([("n", "<u8"), ("dt_ns", "<u8")])
+assert HISTORY_JOINT_CELL_DTYPE.itemsize == 16
+HISTORY_JOINT_HEADER_DTYPE = np.dtype([
+    ("x_bins", "<u4"), ("y_bins", "<u4"), ("n_eligible", "<u8"), ("n_not_carried", "<u8"), ("n_not_finite", "<u8"),
+    ("n_x_below", "<u8"), ("n_x_above", "<u8"), ("n_y_below", "<u8"), ("n_y_above", "<u8"), ("covered_ns", "<u8"),
+    ("w", "<f8"), ("wx", "<f8"), ("wy", "<f8"), ("wxx", "<f8"), ("wyy", "<f8"), ("wxy", "<f8"), ("reserved", "<u8"),
+])
+assert HISTORY_JOINT_HEADER_DTYPE.itemsize == 128
+
+
+def history_joint_args_valid(mx: int, my: int, x_bins: int, y_bins: int, x_lo: float, x_hi: float, y_lo: float,
+                             y_hi: float) -> bool:
+    """Mirror of dynoHistoryJointArgsValid (HistoryReduce.h); the ranges as float32."""
+    with np.errstate(over="ignore"):
+        r = [np.float32(v) for v in (x_lo, x_hi, y_lo, y_hi)]
+    return bool(0 <= mx < len(DERIVED) and 0 <= my < len(DERIVED) and 1 <= x_bins <= HISTORY_JOINT_MAX_BINS
+                and 1 <= y_bins <= HISTORY_JOINT_MAX_BINS and all(np.isfinite(v) for v in r)
+                and r[0] < r[1] and r[2] < r[3])
+
+
+def _history_joint_bin(v: np.ndarray, lo, hi, bins: int) -> np.ndarray:
+    """dynoHistoryJointBin over finite float32 values: two float32 operations, each rounded once."""
+    lo, hi = np.float32(lo), np.float32(hi)
+    with np.errstate(all="ignore"):
+        inv = np.float32(bins) / (hi - lo)
+        t = (v.astype(np.float32) - lo) * inv
+        inside = (t > 0) & (t < np.float32(bins))
+    idx = np.zeros(len(t), dtype=np.int64)  # t not > 0: bin 0
+    idx[inside] = t[inside].astype(np.int64)  # truncation
+    idx[(t > 0) & ~inside] = bins - 1
+    return idx
+
+
+def history_joint_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int, mx: int,
+                            my: int, x_bins: int, y_bins: int, x_lo: float, x_hi: float, y_lo: float, y_hi: float,
+                            phase: int | None = None):
+    """The yardstick of a joint query (SlotFormat.h DynoHistoryJointHeader; the
+    kernels of kernels/history.hip and the host twin historyJoint): (header,
+    joint header, cells) as HISTORY_HEADER_DTYPE, HISTORY_JOINT_HEADER_DTYPE and
+    HISTORY_JOINT_CELL_DTYPE[y_bins * x_bins], cell (ix, iy) at iy * x_bins + ix.
+    Ring arguments as for history_reference (the header is its header at one
+    bucket); mx, my: indices into DERIVED.  The cells and counts are integers:
+    implementations agree with them exactly; the moments are float64 sums."""
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, 1)
+            or not history_joint_args_valid(mx, my, x_bins, y_bins, x_lo, x_hi, y_lo, y_hi)):
+        raise ValueError("history joint query arguments out of range")
+    hdr, _ = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, 1)
+    jh = np.zeros((), dtype=HISTORY_JOINT_HEADER_DTYPE)
+    cells = np.zeros(x_bins * y_bins, dtype=HISTORY_JOINT_CELL_DTYPE)
+    jh["x_bins"], jh["y_bins"] = x_bins, y_bins
+    seqs = np.arange(int(hdr["seq_begin"]), int(hdr["seq_end"]), dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts = x["host_ts_ns"]
+    fresh = (x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1))
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    used = fresh & ((x["flags"] & SLOT_FIRST) == 0) & np.isfinite(dtf) & (dtf > 0)
+    if phase is not None:
+        used &= x["phase"] == np.uint32(phase)
+    mask = derived_mask(x["pass"])
+    carried = used & ((mask >> mx) & (mask >> my) & 1).astype(bool)
+    vx, vy = x["derived"][:, mx], x["derived"][:, my]
+    eligible = carried & np.isfinite(vx) & np.isfinite(vy)
+    jh["n_not_carried"] = int(np.count_nonzero(used & ~carried))
+    jh["n_not_finite"] = int(np.count_nonzero(carried & ~eligible))
+    jh["n_eligible"] = int(np.count_nonzero(eligible))
+    vx, vy, dtf = vx[eligible], vy[eligible], dtf[eligible]
+    jh["n_x_below"], jh["n_x_above"] = np.count_nonzero(vx < np.float32(x_lo)), np.count_nonzero(vx > np.float32(x_hi))
+    jh["n_y_below"], jh["n_y_above"] = np.count_nonzero(vy < np.float32(y_lo)), np.count_nonzero(vy > np.float32(y_hi))
+    cell = _history_joint_bin(vy, y_lo, y_hi, y_bins) * x_bins + _history_joint_bin(vx, x_lo, x_hi, x_bins)
+    dt_ns = (dtf.astype(np.float64) * 1000.0).astype(np.uint64)
+    np.add.at(cells["n"], cell, np.uint64(1))
+    np.add.at(cells["dt_ns"], cell, dt_ns)
+    jh["covered_ns"] = np.sum(dt_ns, dtype=np.uint64)
+    dt, dx, dy = dtf.astype(np.float64), vx.astype(np.float64), vy.astype(np.float64)
+    for name, term in (("w", dt), ("wx", dx * dt), ("wy", dy * dt), ("wxx", dx * dx * dt), ("wyy", dy * dy * dt),
+                       ("wxy", dx * dy * dt)):
+        jh[name] = np.sum(term)
+    return hdr, jh, cells
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

@@ -288,6 +288,15 @@ bool Daemon::start(std::string* err) {
         }
       q["fold"] = req.at("fold");
     }
+    // "joint": {"x", "y", "x_bins", "y_bins", "x_range", "y_range"}: two metrics binned into a grid; "phase" applies
+    if (req.contains("joint") && req.at("joint").isObject()) {
+      for (const char* other : {"fold", "by_phase", "episodes", "quantiles", "buckets"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: joint cannot be combined with ") + other;
+          return j;
+        }
+      q["joint"] = req.at("joint");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

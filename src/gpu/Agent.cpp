@@ -1544,6 +1544,9 @@ void Agent::releaseDevice() {
     freeDev(dHistFoldWs_);
     freeDev(dHistFold_);
     freeHost(hHistFold_);
+    freeDev(dHistJointWs_);
+    freeDev(dHistJoint_);
+    freeHost(hHistJoint_);
     freeDev(dHistEp_);
     freeHost(hHistEp_);
     destroyEvent(histT0_);
@@ -1774,6 +1777,7 @@ Json Agent::stats() const {
   j["history_episode_queries"] = static_cast<unsigned long long>(historyEpisodeQueries_.load());
   j["history_by_phase_queries"] = static_cast<unsigned long long>(historyByPhaseQueries_.load());
   j["history_fold_queries"] = static_cast<unsigned long long>(historyFoldQueries_.load());
+  j["history_joint_queries"] = static_cast<unsigned long long>(historyJointQueries_.load());
   j["last_error"] = lastError_;
   if (sampler_) j["agent"] = sampler_->agent().name;
   if (cfg_.isRoot()) {

@@ -70,7 +70,7 @@ class GpuAgentRegistry {
   // Ask every matching agent (every rank: each GPU's ring holds its own
   // history) for its slot history of a window, reduced on its GPU (IPC "gktr"
   // op "history"; `query` carries t0_ns / t1_ns or last_s, buckets, phase, episodes, by_phase,
-  // fold, metrics).  An answer too large for a datagram comes through the file
+  // fold, joint, metrics).  An answer too large for a datagram comes through the file
   // "<pathPrefix><pid>_r<rank>.json", which is read and removed.
   Json history(const std::vector<int>& pids, const Json& query, const std::string& pathPrefix, const Sender& send,
                int timeoutMs = 8000);
