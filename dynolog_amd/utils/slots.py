@@ -703,6 +703,116 @@ def history_joint_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_sl
     return hdr, jh, cells
 
 
+HISTORY_CORR_MAX_BUCKETS = 64
+_MAT = (MAX_DERIVED, MAX_DERIVED)
+HISTORY_CORR_BUCKET_DTYPE = np.dtype([
+    ("first_seq", "<u8"), ("n_slots", "<u4"), ("n_used", "<u4"), ("dt_us_sum", "<f8"), ("reserved", "<u8"),
+    ("n", "<u4", _MAT), ("w", "<f8", _MAT), ("s", "<f8", _MAT), ("q", "<f8", _MAT), ("p", "<f8", _MAT),
+])
+assert HISTORY_CORR_BUCKET_DTYPE.itemsize == 9248
+HISTORY_CORR_HEADER_DTYPE = np.dtype([("center", "<f4", (MAX_DERIVED,)), ("n_used", "<u8"), ("reserved", "<u8", (7,))])
+assert HISTORY_CORR_HEADER_DTYPE.itemsize == 128
+
+
+def history_corr_args_valid(buckets: int, center) -> bool:
+    """Mirror of dynoHistoryCorrArgsValid (HistoryReduce.h); center None: the automatic one."""
+    if not 1 <= buckets <= HISTORY_CORR_MAX_BUCKETS:
+        return False
+    if center is None:
+        return True
+    with np.errstate(over="ignore"):
+        c = np.asarray(center, dtype=np.float64).astype(np.float32)
+    return bool(c.shape == (MAX_DERIVED,) and np.isfinite(c).all())
+
+
+def history_corr_derive(rec, center):
+    """What a corr answer derives from one DynoHistoryCorrBucket and the centre,
+    over each pair's pairwise-complete set (SlotFormat.h): (mean, var, cov, corr),
+    each [16, 16] float64; mean[i, j] and var[i, j] are metric i's over the slots
+    that also have j.  NaN where n < 2 or a variance is not > 0 (corr), or
+    without samples."""
+    with np.errstate(all="ignore"):
+        w = np.where(rec["n"] > 0, rec["w"], np.nan)
+        sm = rec["s"] / w
+        mean = np.asarray(center, dtype=np.float64)[:, None] + sm
+        var = rec["q"] / w - sm * sm
+        cov = rec["p"] / w - sm * sm.T
+        ok = (rec["n"] >= 2) & (var > 0) & (var.T > 0)
+        corr = np.where(ok, cov / np.sqrt(np.where(ok, var * var.T, 1.0)), np.nan)
+    return mean, var, cov, corr
+
+
+def history_corr_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int,
+                           buckets: int, center=None, phase: int | None = None):
+    """The yardstick of a corr query (SlotFormat.h DynoHistoryCorrBucket; the
+    kernels of kernels/history.hip and the host twin historyCorr): (header, corr
+    header, records, abs, two_pass).  Ring arguments as for history_reference,
+    whose header at `buckets` this returns; center: 16 float32, or None for the
+    window's time-weighted means.  records: HISTORY_CORR_BUCKET_DTYPE[buckets],
+    the integers exact, the sums taken in longdouble and rounded to float64.
+    abs: {"w", "s", "q", "p"} -> [buckets, 16, 16], per element the sum of the
+    absolute values of its terms, which scales the rounding error of any
+    summation order.  two_pass: {"mean", "var", "cov", "corr"} -> [buckets, 16,
+    16] longdouble, centre-free: the weighted mean of each pair's
+    pairwise-complete set first, then the moments about it."""
+    if not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, buckets) or not history_corr_args_valid(buckets, center):
+        raise ValueError("history corr query arguments out of range")
+    hdr, plain = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, buckets, phase)
+    if center is None:
+        _, whole = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, 1, phase)
+        with np.errstate(all="ignore"):
+            center = np.where(whole["w"][0] > 0, (whole["wsum"][0] / whole["w"][0]).astype(np.float32), np.float32(0))
+    ch = np.zeros((), dtype=HISTORY_CORR_HEADER_DTYPE)
+    ch["center"] = np.asarray(center, dtype=np.float32)
+    out = np.zeros(buckets, dtype=HISTORY_CORR_BUCKET_DTYPE)
+    for f in ("first_seq", "n_slots"):
+        out[f] = plain[f]
+    absum = {k: np.zeros((buckets,) + _MAT) for k in "wsqp"}
+    two = {k: np.full((buckets,) + _MAT, np.nan, dtype=np.longdouble) for k in ("mean", "var", "cov", "corr")}
+    seqs = np.arange(int(hdr["seq_begin"]), int(hdr["seq_end"]), dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts = x["host_ts_ns"]
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    used = ((x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1)) & ((x["flags"] & SLOT_FIRST) == 0)
+            & np.isfinite(dtf) & (dtf > 0))
+    if phase is not None:
+        used &= x["phase"] == np.uint32(phase)
+    x, ts = x[used], ts[used]
+    bucket = (((ts - np.uint64(t0)) * np.uint64(buckets)) // np.uint64(t1 - t0)).astype(np.int64)
+    L = np.longdouble
+    for b in range(buckets):
+        xb = x[bucket == b]
+        dt = xb["derived"][:, D["sample_dt_us"]].astype(L)[:, None]
+        v = xb["derived"]
+        m = ((derived_mask(xb["pass"])[:, None] >> np.arange(MAX_DERIVED)) & 1).astype(bool) & np.isfinite(v)
+        mf = m.astype(L)
+        y = np.where(m, v.astype(np.float64) - ch["center"].astype(np.float64), 0.0).astype(L)  # a select: no NaN passes
+        a = dt * y
+        r = out[b]
+        r["n"] = (mf.T @ mf).astype(np.uint32)
+        for k, left, right in (("w", dt * mf, mf), ("s", a, mf), ("q", a * y, mf), ("p", a, y)):
+            r[k] = (left.T @ right).astype(np.float64)
+            absum[k][b] = (np.abs(left).T @ np.abs(right)).astype(np.float64)
+        r["n_used"] = len(xb)
+        r["dt_us_sum"] = float(dt.sum())
+        vl = np.where(m, v, 0).astype(L)
+        for i in range(MAX_DERIVED):
+            for j in range(MAX_DERIVED):
+                both = m[:, i] & m[:, j]
+                if not both.any():
+                    continue
+                wt = dt[both, 0]
+                wsum = wt.sum()
+                di = vl[both, i] - (wt * vl[both, i]).sum() / wsum
+                dj = vl[both, j] - (wt * vl[both, j]).sum() / wsum
+                vi, vj, cij = (wt * di * di).sum() / wsum, (wt * dj * dj).sum() / wsum, (wt * di * dj).sum() / wsum
+                two["mean"][b, i, j], two["var"][b, i, j], two["cov"][b, i, j] = vl[both, i].dot(wt) / wsum, vi, cij
+                if np.count_nonzero(both) >= 2 and vi > 0 and vj > 0:
+                    two["corr"][b, i, j] = cij / np.sqrt(vi * vj)
+    ch["n_used"] = int(out["n_used"].sum())
+    return hdr, ch, out, absum, two
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

@@ -297,6 +297,16 @@ bool Daemon::start(std::string* err) {
         }
       q["joint"] = req.at("joint");
     }
+    // "corr": {"center": "auto" | [16 numbers], "metrics": [..]}: the correlation matrix of all metrics per bucket;
+    // "phase" and "buckets" apply
+    if (req.contains("corr") && req.at("corr").isObject()) {
+      for (const char* other : {"joint", "fold", "by_phase", "episodes", "quantiles"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: corr cannot be combined with ") + other;
+          return j;
+        }
+      q["corr"] = req.at("corr");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";
