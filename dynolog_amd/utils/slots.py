@@ -813,6 +813,122 @@ def history_corr_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slo
     return hdr, ch, out, absum, two
 
 
+HISTORY_PERIOD_MAX_LAGS = 4096
+HISTORY_PERIOD_MAX_CELLS = 1 << 20
+HISTORY_PERIOD_MAX_PEAKS = 16
+HISTORY_LAG_DTYPE = np.dtype([("n", "<u8"), ("sa", "<f8"), ("sb", "<f8"), ("qa", "<f8"), ("qb", "<f8"), ("p", "<f8")])
+assert HISTORY_LAG_DTYPE.itemsize == 48
+HISTORY_PERIOD_HEADER_DTYPE = np.dtype([
+    ("center", "<f4"), ("metric", "<u4"), ("max_lag", "<u4"), ("reserved0", "<u4"), ("cells", "<u8"), ("cell_ns", "<u8"),
+    ("n_eligible", "<u8"), ("n_not_carried", "<u8"), ("n_not_finite", "<u8"), ("n_filled", "<u8"), ("n_collided", "<u8"),
+    ("reserved", "<u8", (7,)),
+])
+assert HISTORY_PERIOD_HEADER_DTYPE.itemsize == 128
+
+
+def history_period_cells(t0: int, t1: int, cell_ns: int) -> int:
+    """Mirror of dynoHistoryPeriodCells: ceil((t1 - t0) / cell_ns), 0 for what is refused anyway."""
+    return -(-(t1 - t0) // cell_ns) if cell_ns >= 1 and t1 > t0 else 0
+
+
+def history_period_args_valid(seq_lo: int, seq_hi: int, t0: int, t1: int, metric: int, cell_ns: int, max_lag: int,
+                              center) -> bool:
+    """Mirror of dynoHistoryPeriodArgsValid (HistoryReduce.h); center None: the automatic one."""
+    if not (0 <= metric < len(DERIVED) and 1 <= cell_ns < 2**64 and 1 <= max_lag <= HISTORY_PERIOD_MAX_LAGS):
+        return False
+    if not 0 <= seq_hi - seq_lo < 2**32:
+        return False
+    if center is not None:
+        with np.errstate(over="ignore"):
+            if not np.isfinite(np.float32(center)):
+                return False
+    return max_lag < history_period_cells(t0, t1, cell_ns) <= HISTORY_PERIOD_MAX_CELLS
+
+
+def history_period_derive(lags, cell_ns: int, min_lag: int = 0, tolerance: float = 0.05,
+                          max_peaks: int = HISTORY_PERIOD_MAX_PEAKS):
+    """Mirror of dynoHistoryLagCorr and dynoHistoryPeriodPeaks (HistoryReduce.h):
+    what a period answer derives from its L + 1 lag records, as a dict: r ([L +
+    1] float64, NaN where it is not defined), peaks ([(lag, r)], the first
+    max_peaks by lag), best (the lag, or None), period_ns and strength."""
+    n = lags["n"].astype(np.float64)
+    with np.errstate(all="ignore"):
+        ma, mb = lags["sa"] / n, lags["sb"] / n
+        va, vb = lags["qa"] / n - ma * ma, lags["qb"] / n - mb * mb
+        ok = (lags["n"] >= 2) & (va > 0) & (vb > 0)
+        r = np.where(ok, (lags["p"] / n - ma * mb) / np.sqrt(np.where(ok, va * vb, 1.0)), np.nan)
+    L = len(lags) - 1
+    out = dict(r=r, peaks=[], best=None, period_ns=None, strength=None)
+    z = next((l for l in range(1, L + 1) if ok[l] and r[l] <= 0), None)
+    if z is None:
+        return out
+    every = [l for l in range(max(z, min_lag), L)
+             if ok[l] and (not ok[l + 1] or r[l] >= r[l + 1]) and (not ok[l - 1] or r[l] > r[l - 1])]
+    out["peaks"] = [(l, float(r[l])) for l in every[:min(max_peaks, HISTORY_PERIOD_MAX_PEAKS)]]
+    if every:
+        top = max(r[l] for l in every)
+        best = next(l for l in every if top - r[l] <= tolerance)
+        out.update(best=best, period_ns=best * cell_ns, strength=float(r[best]))
+    return out
+
+
+def history_period_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int,
+                             metric: int, cell_ns: int, max_lag: int, center=None, phase: int | None = None):
+    """The yardstick of a period query (SlotFormat.h DynoHistoryPeriodHeader; the
+    kernels of kernels/history.hip and the host twin historyPeriod): (header,
+    period header, records, abs).  Ring arguments as for history_reference, whose
+    header at one bucket this returns; center: a float32, or None for the
+    window's time-weighted mean of the metric.  records:
+    HISTORY_LAG_DTYPE[max_lag + 1], n exact, the sums taken in longdouble and
+    rounded to float64.  abs: {"sa", "sb", "qa", "qb", "p"} -> [max_lag + 1], per
+    record the sum of the absolute values of its terms, which scales the
+    rounding error of any summation order."""
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, 1)
+            or not history_period_args_valid(seq_lo, seq_hi, t0, t1, metric, cell_ns, max_lag, center)):
+        raise ValueError("history period query arguments out of range")
+    hdr, whole = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, 1, phase)
+    if center is None:
+        with np.errstate(all="ignore"):
+            w = whole["w"][0][metric]
+            center = np.float32(whole["wsum"][0][metric] / w) if w > 0 else np.float32(0)
+    G = history_period_cells(t0, t1, cell_ns)
+    ph = np.zeros((), dtype=HISTORY_PERIOD_HEADER_DTYPE)
+    ph["center"], ph["metric"], ph["max_lag"], ph["cells"], ph["cell_ns"] = np.float32(center), metric, max_lag, G, cell_ns
+    seqs = np.arange(int(hdr["seq_begin"]), int(hdr["seq_end"]), dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts = x["host_ts_ns"]
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    v = x["derived"][:, metric]
+    used = ((x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1)) & ((x["flags"] & SLOT_FIRST) == 0)
+            & np.isfinite(dtf) & (dtf > 0))
+    if phase is not None:
+        used &= x["phase"] == np.uint32(phase)
+    carried = used & (((derived_mask(x["pass"]) >> metric) & 1) == 1)
+    eligible = carried & np.isfinite(v)
+    ph["n_not_carried"] = int(np.count_nonzero(used & ~carried))
+    ph["n_not_finite"] = int(np.count_nonzero(carried & ~eligible))
+    ph["n_eligible"] = int(np.count_nonzero(eligible))
+    m = np.zeros(G, dtype=bool)
+    xg = np.zeros(G, dtype=np.float32)
+    cell = ((ts[eligible] - np.uint64(t0)) // np.uint64(cell_ns)).astype(np.int64)
+    m[cell] = True
+    xg[cell] = v[eligible]  # in position order: the highest position of a cell is assigned last
+    ph["n_filled"] = int(np.count_nonzero(m))
+    ph["n_collided"] = int(ph["n_eligible"]) - int(ph["n_filled"])
+    LD = np.longdouble
+    y = np.where(m, xg.astype(np.float64) - np.float64(ph["center"]), 0.0).astype(LD)  # a select
+    mf = m.astype(LD)
+    out = np.zeros(max_lag + 1, dtype=HISTORY_LAG_DTYPE)
+    absum = {k: np.zeros(max_lag + 1) for k in ("sa", "sb", "qa", "qb", "p")}
+    for l in range(max_lag + 1):
+        ya, ma, yb, mb = y[:G - l], mf[:G - l], y[l:], mf[l:]
+        out["n"][l] = int(np.count_nonzero(m[:G - l] & m[l:]))
+        for k, t in (("sa", ya * mb), ("sb", ma * yb), ("qa", ya * ya * mb), ("qb", ma * yb * yb), ("p", ya * yb)):
+            out[k][l] = np.float64(t.sum())
+            absum[k][l] = np.float64(np.abs(t).sum())
+    return hdr, ph, out, absum
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

@@ -307,6 +307,16 @@ bool Daemon::start(std::string* err) {
         }
       q["corr"] = req.at("corr");
     }
+    // "period": {"metric", "cell_ms", "max_ms", "min_ms", "center", "tolerance", "lags"}: the step period from the
+    // autocorrelation of one metric; "phase" applies
+    if (req.contains("period") && req.at("period").isObject()) {
+      for (const char* other : {"corr", "joint", "fold", "by_phase", "episodes", "quantiles"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: period cannot be combined with ") + other;
+          return j;
+        }
+      q["period"] = req.at("period");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

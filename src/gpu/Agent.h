@@ -269,6 +269,16 @@ class Agent {
   // stream, wait, the 2 s deadline and the statuses as for history().
   Json historyCorr(uint64_t t0Ns, uint64_t t1Ns, uint32_t buckets, int64_t phase, const float* center,
                    hipStream_t stream, bool wait, uint32_t metricMask = ~0u);
+  // How long a step is, without a marker in the job (SlotFormat.h
+  // DynoHistoryPeriodHeader): the autocorrelation of `metric` over the window
+  // on cells of cellNs for the lags 0 .. maxLag, its peaks from minLag on and
+  // the best one (period_ns, strength), with "lags" ([lag, n, r]) when
+  // wantLags.  center: one float the sums are taken about, or nullptr for the
+  // window's time-weighted mean; tolerance: how far below the highest peak a
+  // peak of a lower lag may lie and still be the best.  phase, stream, wait,
+  // the 2 s deadline and the statuses as for history().
+  Json historyPeriod(uint64_t t0Ns, uint64_t t1Ns, int64_t phase, uint32_t metric, uint64_t cellNs, uint32_t maxLag,
+                     uint32_t minLag, const float* center, double tolerance, bool wantLags, hipStream_t stream, bool wait);
   // The id Python's GpuAgent.phase gives a phase path ("step/forward"): FNV-1a, 0 = no phase
   static uint32_t phaseIdOf(const std::string& path);
   std::shared_ptr<MemoryLogger::Store> memoryStore() const { return memStore_; }

@@ -286,13 +286,14 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
       },
       timeoutMs, send);
   // an answer too large for a datagram left its buckets (an episode query: its episodes, a fold: its
-  // profile, a joint query: its cells) in the named file
+  // profile, a joint query: its cells, a period query: its lags) in the named file
   for (auto& r : out["results"].asArray()) {
     if (!r.isObject()) continue;
     const char* big = r.contains("buckets_path")    ? "buckets"
                       : r.contains("episodes_path") ? "episodes"
                       : r.contains("profile_path")  ? "profile"
                       : r.contains("cells_path")    ? "cells"
+                      : r.contains("lags_path")     ? "lags"
                                                     : nullptr;
     if (!big) continue;
     r.asObject().erase(std::string(big) + "_path");
