@@ -929,6 +929,116 @@ def history_period_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_s
     return hdr, ph, out, absum
 
 
+HISTORY_SHIFT_MAX_LISTED = 1024
+HISTORY_SHIFT_DTYPE = np.dtype([("cell", "<u8"), ("t_ns", "<u8"), ("n_before", "<u4"), ("n_after", "<u4"),
+                                ("mean_before", "<f8"), ("mean_after", "<f8"), ("delta", "<f8")])
+assert HISTORY_SHIFT_DTYPE.itemsize == 48
+HISTORY_SHIFT_HEADER_DTYPE = np.dtype([
+    ("metric", "<u4"), ("window", "<u4"), ("min_n", "<u4"), ("min_delta", "<f4"), ("cells", "<u8"), ("cell_ns", "<u8"),
+    ("n_eligible", "<u8"), ("n_not_carried", "<u8"), ("n_not_finite", "<u8"), ("n_filled", "<u8"), ("n_collided", "<u8"),
+    ("n_clamped", "<u8"), ("n_valid", "<u8"), ("n_shifts", "<u4"), ("n_up", "<u4"), ("n_down", "<u4"), ("returned", "<u4"),
+    ("strongest_cell", "<u8"), ("strongest_delta", "<f8"), ("reserved", "<u8", (1,)),
+])
+assert HISTORY_SHIFT_HEADER_DTYPE.itemsize == 128
+
+
+def history_shift_args_valid(seq_lo: int, seq_hi: int, t0: int, t1: int, metric: int, cell_ns: int, window: int,
+                             min_n: int, min_delta: float, max_shifts: int) -> bool:
+    """Mirror of dynoHistoryShiftArgsValid (HistoryReduce.h)."""
+    if not (0 <= metric < len(DERIVED) and 1 <= cell_ns < 2**64 and 1 <= min_n <= window < 2**32):
+        return False
+    if not 0 <= seq_hi - seq_lo < 2**32 or not 0 <= max_shifts <= HISTORY_SHIFT_MAX_LISTED:
+        return False
+    with np.errstate(over="ignore"):
+        if not (np.isfinite(np.float32(min_delta)) and np.float32(min_delta) >= 0):
+            return False
+    return window < history_period_cells(t0, t1, cell_ns) <= HISTORY_PERIOD_MAX_CELLS
+
+
+def _highest_of_next(key: np.ndarray, span: int) -> np.ndarray:
+    """out[i] = max(key[i : i + span]) by doubling spans (zeros past the end)."""
+    n = len(key)
+    cur, have = key.copy(), 1
+    ahead = lambda a, by: np.concatenate([a[by:], np.zeros(min(by, n), dtype=a.dtype)])
+    while have * 2 <= span:
+        cur = np.maximum(cur, ahead(cur, have))
+        have *= 2
+    return np.maximum(cur, ahead(cur, span - have))
+
+
+def history_shifts_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int, metric: int,
+                             cell_ns: int, window: int, min_n: int, min_delta: float = 0.0, max_shifts: int = 64,
+                             phase: int | None = None):
+    """The yardstick of a shift query (SlotFormat.h DynoHistoryShiftHeader; the
+    kernels of kernels/history.hip and the host twin historyShifts): (header,
+    shift header, records[returned]).  Ring arguments as for history_reference,
+    whose header at one bucket this returns.  Integer sums and correctly rounded
+    float64 steps only: every byte is the definition's."""
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, 1)
+            or not history_shift_args_valid(seq_lo, seq_hi, t0, t1, metric, cell_ns, window, min_n, min_delta, max_shifts)):
+        raise ValueError("history shift query arguments out of range")
+    hdr, _ = history_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, 1, phase)
+    G, W = history_period_cells(t0, t1, cell_ns), window
+    sh = np.zeros((), dtype=HISTORY_SHIFT_HEADER_DTYPE)
+    sh["metric"], sh["window"], sh["min_n"], sh["min_delta"], sh["cells"], sh["cell_ns"] = metric, W, min_n, min_delta, G, cell_ns
+    seqs = np.arange(int(hdr["seq_begin"]), int(hdr["seq_end"]), dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts = x["host_ts_ns"]
+    dtf = x["derived"][:, D["sample_dt_us"]]
+    v = x["derived"][:, metric]
+    used = ((x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1)) & ((x["flags"] & SLOT_FIRST) == 0)
+            & np.isfinite(dtf) & (dtf > 0))
+    if phase is not None:
+        used &= x["phase"] == np.uint32(phase)
+    carried = used & (((derived_mask(x["pass"]) >> metric) & 1) == 1)
+    eligible = carried & np.isfinite(v)
+    sh["n_not_carried"] = int(np.count_nonzero(used & ~carried))
+    sh["n_not_finite"] = int(np.count_nonzero(carried & ~eligible))
+    sh["n_eligible"] = int(np.count_nonzero(eligible))
+    m = np.zeros(G, dtype=bool)
+    xg = np.zeros(G, dtype=np.float32)
+    cell = ((ts[eligible] - np.uint64(t0)) // np.uint64(cell_ns)).astype(np.int64)
+    m[cell] = True
+    xg[cell] = v[eligible]  # in position order: the highest position of a cell is assigned last
+    sh["n_filled"] = int(np.count_nonzero(m))
+    sh["n_collided"] = int(sh["n_eligible"]) - int(sh["n_filled"])
+    d = xg.astype(np.float64) * 2.0**20
+    sh["n_clamped"] = int(np.count_nonzero(m & (np.abs(d) > 2.0**42)))
+    q = np.where(m, np.rint(np.clip(d, -2.0**42, 2.0**42)), 0.0).astype(np.int64)
+    N = np.concatenate([[0], np.cumsum(m, dtype=np.int64)])
+    Q = np.concatenate([[0], np.cumsum(q, dtype=np.int64)])
+    k = np.arange(1, G, dtype=np.int64)
+    a, b = np.maximum(k, W) - W, np.minimum(G, k + W)
+    nb, na, sb, sa = N[k] - N[a], N[b] - N[k], Q[k] - Q[a], Q[b] - Q[k]
+    valid = (nb >= min_n) & (na >= min_n)
+    sh["n_valid"] = int(np.count_nonzero(valid))
+    nbf, naf = np.where(valid, nb, 1).astype(np.float64), np.where(valid, na, 1).astype(np.float64)  # valid: n >= 1
+    mean_b, mean_a = sb.astype(np.float64) / nbf * 2.0**-20, sa.astype(np.float64) / naf * 2.0**-20
+    delta = (sa.astype(np.float64) / naf - sb.astype(np.float64) / nbf) * 2.0**-20
+    key = np.zeros(G, dtype=np.uint64)
+    key[1:] = np.where(valid, np.abs(delta).view(np.uint64), np.uint64(0))
+    sh["strongest_cell"] = 2**64 - 1
+    if key.max() > 0:
+        top = int(np.argmax(key))  # the first of the highest
+        sh["strongest_cell"], sh["strongest_delta"] = top, delta[top - 1]
+    nxt = _highest_of_next(np.concatenate([np.zeros(W, dtype=np.uint64), key, np.zeros(W + 1, dtype=np.uint64)]), W)
+    kk = np.arange(G)
+    before, after = nxt[kk], nxt[kk + 1 + W]  # the highest key of [k - W, k) and of (k, k + W]
+    floor = np.abs(np.float64(np.float32(min_delta))).view(np.uint64)
+    is_shift = (key > 0) & (key >= floor) & (key > before) & (key >= after)
+    at = np.flatnonzero(is_shift)
+    sh["n_shifts"] = len(at)
+    sh["n_up"] = int(np.count_nonzero(delta[at - 1] > 0))
+    sh["n_down"] = int(np.count_nonzero(delta[at - 1] < 0))
+    at = at[:max_shifts]
+    sh["returned"] = len(at)
+    out = np.zeros(len(at), dtype=HISTORY_SHIFT_DTYPE)
+    out["cell"], out["t_ns"] = at, np.uint64(t0) + at.astype(np.uint64) * np.uint64(cell_ns)
+    out["n_before"], out["n_after"] = nb[at - 1], na[at - 1]
+    out["mean_before"], out["mean_after"], out["delta"] = mean_b[at - 1], mean_a[at - 1], delta[at - 1]
+    return hdr, sh, out
+
+
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):
     """Mirror of planGatherRange (src/gpu/GatherPlan.h): (first, count, dropped, backlog).
     Oldest pending slots first, at most cap; pending slots more than half the

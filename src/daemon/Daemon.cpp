@@ -317,6 +317,16 @@ bool Daemon::start(std::string* err) {
         }
       q["period"] = req.at("period");
     }
+    // "shifts": {"metric", "window_ms", "min_delta", "cell_ms", "min_fill", "max_shifts"}: the moments at which one
+    // metric changed level; "phase" applies
+    if (req.contains("shifts") && req.at("shifts").isObject()) {
+      for (const char* other : {"period", "corr", "joint", "fold", "by_phase", "episodes", "quantiles"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: shifts cannot be combined with ") + other;
+          return j;
+        }
+      q["shifts"] = req.at("shifts");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

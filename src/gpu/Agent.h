@@ -279,6 +279,14 @@ class Agent {
   // the 2 s deadline and the statuses as for history().
   Json historyPeriod(uint64_t t0Ns, uint64_t t1Ns, int64_t phase, uint32_t metric, uint64_t cellNs, uint32_t maxLag,
                      uint32_t minLag, const float* center, double tolerance, bool wantLags, hipStream_t stream, bool wait);
+  // Since when (SlotFormat.h DynoHistoryShiftHeader): the boundaries of the
+  // window's cells of cellNs at which `metric` changed level by minDelta or
+  // more between the `window` cells before and after, each side with at least
+  // minN filled cells; the strongest boundary and the first maxShifts shifts in
+  // time order.  phase, stream, wait, the 2 s deadline and the statuses as for
+  // history().
+  Json historyShifts(uint64_t t0Ns, uint64_t t1Ns, int64_t phase, uint32_t metric, uint64_t cellNs, uint32_t window,
+                     uint32_t minN, float minDelta, uint32_t maxShifts, hipStream_t stream, bool wait);
   // The id Python's GpuAgent.phase gives a phase path ("step/forward"): FNV-1a, 0 = no phase
   static uint32_t phaseIdOf(const std::string& path);
   std::shared_ptr<MemoryLogger::Store> memoryStore() const { return memStore_; }

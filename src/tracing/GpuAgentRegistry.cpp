@@ -286,7 +286,7 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
       },
       timeoutMs, send);
   // an answer too large for a datagram left its buckets (an episode query: its episodes, a fold: its
-  // profile, a joint query: its cells, a period query: its lags) in the named file
+  // profile, a joint query: its cells, a period query: its lags, a shift query: its shifts) in the named file
   for (auto& r : out["results"].asArray()) {
     if (!r.isObject()) continue;
     const char* big = r.contains("buckets_path")    ? "buckets"
@@ -294,6 +294,7 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
                       : r.contains("profile_path")  ? "profile"
                       : r.contains("cells_path")    ? "cells"
                       : r.contains("lags_path")     ? "lags"
+                      : r.contains("shifts_path")   ? "shifts"
                                                     : nullptr;
     if (!big) continue;
     r.asObject().erase(std::string(big) + "_path");
