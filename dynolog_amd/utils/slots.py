@@ -1,6 +1,8 @@
 """NumPy views of the native sampler formats (mirror of src/gpu/SlotFormat.h)."""
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 SLOT_BYTES = 256
@@ -1037,6 +1039,145 @@ def history_shifts_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_s
     out["n_before"], out["n_after"] = nb[at - 1], na[at - 1]
     out["mean_before"], out["mean_after"], out["delta"] = mean_b[at - 1], mean_a[at - 1], delta[at - 1]
     return hdr, sh, out
+
+
+HISTORY_MATCH_MIN_CELLS = 4
+HISTORY_MATCH_MAX_CELLS = 4096
+HISTORY_MATCH_MAX_LISTED = 1024
+HISTORY_MATCH_NONE = 0x7FC00000  # r's bit pattern at a position without a score
+HISTORY_MATCH_DTYPE = np.dtype([("cell", "<u4"), ("n", "<u4"), ("r", "<f4"), ("self", "<u4")])
+assert HISTORY_MATCH_DTYPE.itemsize == 16
+HISTORY_MATCH_HEADER_DTYPE = np.dtype([
+    ("center", "<f4"), ("metric", "<u4"), ("tpl_cells", "<u4"), ("tpl_filled", "<u4"), ("cells", "<u8"), ("cell_ns", "<u8"),
+    ("n_eligible", "<u8"), ("n_not_carried", "<u8"), ("n_not_finite", "<u8"), ("n_filled", "<u8"), ("n_collided", "<u8"),
+    ("tpl_cell", "<u8"), ("min_n", "<u4"), ("excl", "<u4"), ("min_r", "<f4"), ("min_fill", "<f4"), ("n_scored", "<u8"),
+    ("n_matches", "<u4"), ("returned", "<u4"), ("best_cell", "<u8"), ("best_r", "<f4"), ("best_n", "<u4"),
+])
+assert HISTORY_MATCH_HEADER_DTYPE.itemsize == 128
+HISTORY_MATCH_SUMS = ("n", "st", "sx", "qt", "qx", "pp")
+
+
+def history_match_args_valid(seq_lo: int, seq_hi: int, t0: int, t1: int, metric: int, cell_ns: int, tpl_t0_ns: int,
+                             tpl_t1_ns: int, min_r: float, min_fill: float, max_matches: int, center) -> bool:
+    """Mirror of dynoHistoryMatchArgsValid (HistoryReduce.h); center None: the automatic one."""
+    if not (0 <= metric < len(DERIVED) and 1 <= cell_ns < 2**64 and 1 <= max_matches <= HISTORY_MATCH_MAX_LISTED):
+        return False
+    if not 0 <= seq_hi - seq_lo < 2**32:
+        return False
+    with np.errstate(over="ignore"):
+        if center is not None and not np.isfinite(np.float32(center)):
+            return False
+        if not (-1 <= np.float32(min_r) <= 1 and 0 <= np.float32(min_fill) <= 1):  # NaN fails both
+            return False
+    G = history_period_cells(t0, t1, cell_ns)
+    if not (1 <= G <= HISTORY_PERIOD_MAX_CELLS and t0 <= tpl_t0_ns < tpl_t1_ns <= t1):
+        return False
+    a, m = (tpl_t0_ns - t0) // cell_ns, history_period_cells(tpl_t0_ns, tpl_t1_ns, cell_ns)
+    return HISTORY_MATCH_MIN_CELLS <= m <= HISTORY_MATCH_MAX_CELLS and a + m <= G
+
+
+def history_match_score(sums: np.ndarray, min_n: int):
+    """Mirror of dynoHistoryMatchScore (SlotFormat.h): sums [P, 6] float64 (n, st,
+    sx, qt, qx, pp) -> (r [P] float32, HISTORY_MATCH_NONE's NaN where a position
+    has no score; n [P] uint32).  The same float64 steps in the same order, each
+    rounded once: the same sums give the same bits."""
+    nd, st, sx, qt, qx, pp = (np.ascontiguousarray(sums[:, k], dtype=np.float64) for k in range(6))
+    n = nd.astype(np.uint32)
+    with np.errstate(all="ignore"):
+        vt, vx = nd * qt - st * st, nd * qx - sx * sx
+        ok = (n >= max(min_n, 2)) & (vt > 0) & (vx > 0)
+        r = ((nd * pp - st * sx) / np.sqrt(np.where(ok, vt * vx, 1.0))).astype(np.float32)
+    bits = np.where(ok, r.view(np.uint32), np.uint32(HISTORY_MATCH_NONE)).astype(np.uint32)
+    return bits.view(np.float32), n
+
+
+def history_match_key(r: np.ndarray) -> np.ndarray:
+    """Mirror of dynoHistoryMatchKey: 0 without a score, otherwise ordered as the floats are."""
+    bits = np.ascontiguousarray(r, dtype=np.float32).view(np.uint32)
+    key = np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.uint32)
+    return np.where(bits == np.uint32(HISTORY_MATCH_NONE), np.uint32(0), key).astype(np.uint32)
+
+
+def history_match_derive(r: np.ndarray, n: np.ndarray, tpl_cell: int, excl: int, min_r: float, max_matches: int) -> dict:
+    """The match rule of SlotFormat.h over a profile (r, n): n_scored, n_matches,
+    returned, best_cell (2^64 - 1: none), best_r, best_n and matches
+    (HISTORY_MATCH_DTYPE[returned], in order of the cell)."""
+    key = history_match_key(r)
+    P = len(key)
+    nxt = _highest_of_next(np.concatenate([np.zeros(excl, dtype=np.uint32), key, np.zeros(excl + 1, dtype=np.uint32)]), excl)
+    pp = np.arange(P)
+    before, after = nxt[pp], nxt[pp + 1 + excl]  # the highest key of [p - excl, p) and of (p, p + excl]
+    with np.errstate(invalid="ignore"):
+        is_match = (key > 0) & (r >= np.float32(min_r)) & (key > before) & (key >= after)
+    at = np.flatnonzero(is_match)
+    out = dict(n_scored=int(np.count_nonzero(key)), n_matches=len(at), best_cell=2**64 - 1, best_r=np.float32(0), best_n=0)
+    others = at[at != tpl_cell]
+    if len(others):
+        best = int(others[np.argmax(key[others])])  # the first of the highest
+        out.update(best_cell=best, best_r=r[best], best_n=int(n[best]))
+    at = at[:max_matches]
+    recs = np.zeros(len(at), dtype=HISTORY_MATCH_DTYPE)
+    recs["cell"], recs["n"], recs["r"], recs["self"] = at, n[at], r[at], at == tpl_cell
+    out.update(returned=len(at), matches=recs)
+    return out
+
+
+def history_match_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_slots: int, t0: int, t1: int, metric: int,
+                            cell_ns: int, tpl_t0_ns: int, tpl_t1_ns: int, min_r: float = 0.8, min_fill: float = 0.5,
+                            max_matches: int = 64, center=None, phase: int | None = None):
+    """The yardstick of a match query (SlotFormat.h DynoHistoryMatchHeader; the
+    kernels of kernels/history.hip and the host twin historyMatch): (header,
+    match header, sums, abs).  Ring arguments as for history_reference, whose
+    header at one bucket this returns; center: a float32, or None for the
+    window's time-weighted mean.  The match header carries what the grid
+    decides (the counts, the template, min_n, excl); n_scored, the matches and
+    best come from history_match_score and history_match_derive.  sums: float64
+    [G - m + 1, 6] in the order of HISTORY_MATCH_SUMS, n exact, the others taken
+    in longdouble and rounded.  abs: the same shape, per sum the sum of the
+    absolute values of its terms, which scales the rounding error of any
+    summation order."""
+    if (not history_args_valid(ring_slots, seq_lo, seq_hi, t0, t1, 1)
+            or not history_match_args_valid(seq_lo, seq_hi, t0, t1, metric, cell_ns, tpl_t0_ns, tpl_t1_ns, min_r, min_fill,
+                                            max_matches, center)):
+        raise ValueError("history match query arguments out of range")
+    # the header, the centre and the grid's counts are the period query's (G >= m >= 4: a max_lag of 1 stands in)
+    hdr, ph, _, _ = history_period_reference(slots, seq_lo, seq_hi, ring_slots, t0, t1, metric, cell_ns, 1, center, phase)
+    G = history_period_cells(t0, t1, cell_ns)
+    a, m = (tpl_t0_ns - t0) // cell_ns, history_period_cells(tpl_t0_ns, tpl_t1_ns, cell_ns)
+    mh = np.zeros((), dtype=HISTORY_MATCH_HEADER_DTYPE)
+    for f in ("center", "metric", "cells", "cell_ns", "n_eligible", "n_not_carried", "n_not_finite", "n_filled", "n_collided"):
+        mh[f] = ph[f]
+    mh["tpl_cell"], mh["tpl_cells"], mh["excl"], mh["min_r"], mh["min_fill"] = a, m, max(1, m // 2), min_r, min_fill
+    mark, y = _history_grid(slots, hdr, ring_slots, t0, t1, metric, cell_ns, mh["center"], phase)
+    tm, ty = mark[a:a + m], y[a:a + m]
+    mh["tpl_filled"] = int(np.count_nonzero(tm))
+    mh["min_n"] = max(2, math.ceil(float(np.float32(min_fill)) * int(mh["tpl_filled"])))
+    P = G - m + 1
+    sums, absum = np.zeros((P, 6)), np.zeros((P, 6))
+    for p in range(P):
+        both = tm & mark[p:p + m]
+        t, x = ty[both], y[p:p + m][both]
+        sums[p, 0] = absum[p, 0] = len(t)
+        for k, term in enumerate((t, x, t * t, x * x, t * x), start=1):
+            sums[p, k], absum[p, k] = np.float64(term.sum()), np.float64(np.abs(term).sum())
+    return hdr, mh, sums, absum
+
+
+def _history_grid(slots, hdr, ring_slots, t0, t1, metric, cell_ns, center, phase):
+    """(m_g as bool, y_g as longdouble) of a period or match query (SlotFormat.h THE GRID)."""
+    G = history_period_cells(t0, t1, cell_ns)
+    seqs = np.arange(int(hdr["seq_begin"]), int(hdr["seq_end"]), dtype=np.uint64)
+    x = slots[(seqs & np.uint64(ring_slots - 1)).astype(np.int64)]
+    ts, dtf, v = x["host_ts_ns"], x["derived"][:, D["sample_dt_us"]], x["derived"][:, metric]
+    eligible = ((x["seq"] == seqs) & (ts >= np.uint64(t0)) & (ts < np.uint64(t1)) & ((x["flags"] & SLOT_FIRST) == 0)
+                & np.isfinite(dtf) & (dtf > 0) & (((derived_mask(x["pass"]) >> metric) & 1) == 1) & np.isfinite(v))
+    if phase is not None:
+        eligible &= x["phase"] == np.uint32(phase)
+    mark, xg = np.zeros(G, dtype=bool), np.zeros(G, dtype=np.float32)
+    cell = ((ts[eligible] - np.uint64(t0)) // np.uint64(cell_ns)).astype(np.int64)
+    mark[cell] = True
+    xg[cell] = v[eligible]  # in position order: the highest position of a cell is assigned last
+    return mark, np.where(mark, xg.astype(np.float64) - np.float64(center), 0.0).astype(np.longdouble)
 
 
 def plan_gather_range(head: int, gathered: int, cap: int, ring_capacity: int):

@@ -327,6 +327,16 @@ bool Daemon::start(std::string* err) {
         }
       q["shifts"] = req.at("shifts");
     }
+    // "match": {"metric", "tpl_t0_ns", "tpl_t1_ns", "min_r", "cell_ms", "min_fill", "max_matches", "center"}: where a
+    // stretch of the window recurs; "phase" applies
+    if (req.contains("match") && req.at("match").isObject()) {
+      for (const char* other : {"shifts", "period", "corr", "joint", "fold", "by_phase", "episodes", "quantiles"})
+        if (q.contains(other)) {
+          j["status"] = std::string("failed: match cannot be combined with ") + other;
+          return j;
+        }
+      q["match"] = req.at("match");
+    }
     static std::atomic<uint64_t> serial{0};
     const std::string prefix =
         "/tmp/dynolog_history_" + std::to_string(getpid()) + "_" + std::to_string(serial++) + "_";

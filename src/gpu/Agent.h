@@ -287,6 +287,17 @@ class Agent {
   // history().
   Json historyShifts(uint64_t t0Ns, uint64_t t1Ns, int64_t phase, uint32_t metric, uint64_t cellNs, uint32_t window,
                      uint32_t minN, float minDelta, uint32_t maxShifts, hipStream_t stream, bool wait);
+  // When else did this happen (SlotFormat.h DynoHistoryMatchHeader): the
+  // positions of the window's cells of cellNs at which the stretch [tplT0Ns,
+  // tplT1Ns) of the same window recurs with a correlation of minR or more,
+  // gaps left out, each position with at least max(2, ceil(minFill * the
+  // template's filled cells)) pairs; the best one and the first maxMatches in
+  // time order.  center: one float, or nullptr for the window's time-weighted
+  // mean.  phase, stream, wait, the 2 s deadline and the statuses as for
+  // history().
+  Json historyMatch(uint64_t t0Ns, uint64_t t1Ns, int64_t phase, uint32_t metric, uint64_t cellNs, uint64_t tplT0Ns,
+                    uint64_t tplT1Ns, float minR, float minFill, uint32_t maxMatches, const float* center, hipStream_t stream,
+                    bool wait);
   // The id Python's GpuAgent.phase gives a phase path ("step/forward"): FNV-1a, 0 = no phase
   static uint32_t phaseIdOf(const std::string& path);
   std::shared_ptr<MemoryLogger::Store> memoryStore() const { return memStore_; }

@@ -286,7 +286,8 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
       },
       timeoutMs, send);
   // an answer too large for a datagram left its buckets (an episode query: its episodes, a fold: its
-  // profile, a joint query: its cells, a period query: its lags, a shift query: its shifts) in the named file
+  // profile, a joint query: its cells, a period query: its lags, a shift query: its shifts, a match
+  // query: its matches) in the named file
   for (auto& r : out["results"].asArray()) {
     if (!r.isObject()) continue;
     const char* big = r.contains("buckets_path")    ? "buckets"
@@ -295,6 +296,7 @@ Json GpuAgentRegistry::history(const std::vector<int>& pids, const Json& query, 
                       : r.contains("cells_path")    ? "cells"
                       : r.contains("lags_path")     ? "lags"
                       : r.contains("shifts_path")   ? "shifts"
+                      : r.contains("matches_path")  ? "matches"
                                                     : nullptr;
     if (!big) continue;
     r.asObject().erase(std::string(big) + "_path");
