@@ -694,7 +694,9 @@ def history_joint_reference(slots: np.ndarray, seq_lo: int, seq_hi: int, ring_sl
     jh["n_x_below"], jh["n_x_above"] = np.count_nonzero(vx < np.float32(x_lo)), np.count_nonzero(vx > np.float32(x_hi))
     jh["n_y_below"], jh["n_y_above"] = np.count_nonzero(vy < np.float32(y_lo)), np.count_nonzero(vy > np.float32(y_hi))
     cell = _history_joint_bin(vy, y_lo, y_hi, y_bins) * x_bins + _history_joint_bin(vx, x_lo, x_hi, x_bins)
-    dt_ns = (dtf.astype(np.float64) * 1000.0).astype(np.uint64)
+    d = dtf.astype(np.float64) * 1000.0
+    big = d >= 2.0**64  # dynoHistoryJointDtNs: 2^64 - 1
+    dt_ns = np.where(big, np.uint64(2**64 - 1), np.where(big, 0.0, d).astype(np.uint64))
     np.add.at(cells["n"], cell, np.uint64(1))
     np.add.at(cells["dt_ns"], cell, dt_ns)
     jh["covered_ns"] = np.sum(dt_ns, dtype=np.uint64)

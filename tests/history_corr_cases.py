@@ -115,17 +115,31 @@ def assert_same(got, case):
     64 * n * 2^-53 * (1 + max((mean - c)^2 / var)) of the centre-free two-pass
     one (the variance about a centre off the mean loses that much), and None in
     the same places."""
-    label, kw = case[0], case[7]
+    assert_center(got, case)
+    assert_raw(got, case)
+    assert_derived(got, case)
+
+
+def assert_center(got, case):
+    """The centre of assert_same: the given one bit for bit, the automatic one within one float32 ulp."""
+    label, kw, ch = case[0], case[7], got[2]
     assert got[0] == 0, (label, got[0])
-    rc, hdr, ch, recs, past = got
-    ref_hdr, ref_ch, ref, absum, two = reference(case, ch["center"])
-    for f in S.HISTORY_HEADER_DTYPE.names:
-        assert int(hdr[f]) == int(ref_hdr[f]), (label, f, int(hdr[f]), int(ref_hdr[f]))
     if kw["center"] is None:
         auto = reference(case, None)[1]["center"]
         assert (np.abs(ch["center"] - auto) <= np.spacing(np.abs(auto))).all(), (label, ch["center"], auto)
     else:
         assert ch["center"].tobytes() == np.asarray(kw["center"], dtype=np.float32).tobytes(), label
+
+
+def assert_raw(got, case):
+    """The records of assert_same at the answer's own centre: the headers, every integer, w, s, q, p and
+    dt_us_sum, the record past the end."""
+    label = case[0]
+    assert got[0] == 0, (label, got[0])
+    rc, hdr, ch, recs, past = got
+    ref_hdr, ref_ch, ref, absum, two = reference(case, ch["center"])
+    for f in S.HISTORY_HEADER_DTYPE.names:
+        assert int(hdr[f]) == int(ref_hdr[f]), (label, f, int(hdr[f]), int(ref_hdr[f]))
     assert int(ch["n_used"]) == int(ref_ch["n_used"]) and not ch["reserved"].any(), (label, ch)
     for f in ("first_seq", "n_slots", "n_used", "reserved", "n"):
         np.testing.assert_array_equal(recs[f], ref[f], err_msg=f"{label} {f}")
@@ -134,6 +148,15 @@ def assert_same(got, case):
         err, bound = np.abs(recs[f] - ref[f]), (n + 4) * 2.0**-52 * absum[f]
         assert (err <= bound).all(), (label, f, np.argwhere(err > bound)[:4], err.max())
     np.testing.assert_allclose(recs["dt_us_sum"], ref["dt_us_sum"], rtol=(ref["n_used"].max() + 4) * 2.0**-52, atol=0)
+    assert (past.view(np.uint8) == 0xEE).all(), f"{label}: a record past the end was written"
+
+
+def assert_derived(got, case):
+    """The derived corr of assert_same against the centre-free two-pass one."""
+    label = case[0]
+    rc, hdr, ch, recs, past = got
+    ref_hdr, ref_ch, ref, absum, two = reference(case, ch["center"])
+    n = ref["n"].astype(np.float64)
     for b in range(len(recs)):
         mean, var, _, corr = S.history_corr_derive(recs[b], ch["center"])
         want = two["corr"][b].astype(np.float64)
@@ -143,7 +166,6 @@ def assert_same(got, case):
         bound = 64 * n[b] * 2.0**-53 * (1 + np.maximum(off, off.T))
         err = np.where(ok, np.abs(corr - want), 0.0)
         assert (err <= bound).all(), (label, b, np.argwhere(err > bound)[:4], err.max())
-    assert (past.view(np.uint8) == 0xEE).all(), f"{label}: a record past the end was written"
 
 
 REFUSED_CORRS = [
